@@ -29,9 +29,22 @@ second half of the metric): GPU stream 0 against the oracle, both free-running f
 on identical features and priors.  cpu_all_cores: one oracle replica per core (stream c on
 core c), map building untimed, the K timed frames of every replica bracketed by a barrier.
 
-Usage: python bench.py [--gpus N --steps K --warmup W --streams B]; for N > 1 launch with
-torch.distributed.run, one rank per GPU (streams shard across ranks, no data-path
-collective: "scaling": "weak").
+A plain run does what the headline needs and no more: inputs, map building, warmup, the K
+timed steps, the result line (value, ms_per_step, and the kernel families / roofline / stage
+times that the timed steps and the input stages measure as they run).  --full adds every other
+leg, each a run of its own: cpu_baseline, pose_rmse_vs_cpu and cpu_all_cores, the
+exact_voxel_order leg, single_stream, the batched stages, depth association, VO solve, the
+one-stream pipeline and the sharded leg; the --no-* options and --shard-streams 0 then switch
+single legs off (select_legs below; --shard-streams N > 0 without --full is an error).
+
+--dump-outputs DIR writes, after the timed steps, what their last step left with the caller as
+DIR/<name>.npy (dump_outputs below).  The inputs depend on the arguments alone (seeded
+generator, deterministic feature stages), so two builds run with the same arguments can be
+compared output for output.
+
+Usage: python bench.py [--gpus N --steps K --warmup W --streams B --full --dump-outputs DIR]; for
+N > 1 launch with torch.distributed.run, one rank per GPU (streams shard across ranks, no
+data-path collective: "scaling": "weak").
 """
 import argparse
 import json
@@ -45,6 +58,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, "vloam-noted_amd"))
 
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: all files together stay below this
+DUMP_MAP_STREAMS = 4  # streams whose map cloud is written (a fixed, seeded sample)
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s (spec)
 SHARD_LEG_LIMIT_S = 240.0  # watchdog of the sharded leg (its RCCL collectives are the only exchange)
 
@@ -67,6 +82,11 @@ def parse():
     ap.add_argument("--cpu-cores", type=int, default=0,
                     help="oracle replicas of the all-cores CPU figure (0: min(16, usable cores): the GPU pool "
                          "allots 16 host CPUs to one GPU, whatever the affinity mask shows)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline (CPU baselines, exact order, single stream, "
+                         "batched stages, depth / VO / pipeline stages, sharded leg); off: the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the results of the last timed step as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-prof", action="store_true", help="no per-launch HIP events")
     ap.add_argument("--prior", choices=["odometry", "drift"], default="odometry",
@@ -77,8 +97,9 @@ def parse():
     ap.add_argument("--exact-voxel-order", type=int, choices=[0, 1], default=0,
                     help="mapper VoxelGrids of the headline in PCL's summation order (1) or input order (0, the "
                          "library default; maps differ by summation-order ulps)")
-    ap.add_argument("--shard-streams", type=int, default=32,
-                    help="streams of the sharded leg (every stream split over all ranks; 0: skip the leg)")
+    ap.add_argument("--shard-streams", type=int, default=None,
+                    help="streams of the sharded leg, a leg of --full (every stream split over all ranks; default "
+                         "32; 0: skip the leg); a value above 0 without --full is an error")
     ap.add_argument("--pipelined", action="store_true",
                     help="(the default for the timed steps; kept for older command lines)")
     ap.add_argument("--pose-first", action="store_true",
@@ -96,6 +117,22 @@ def parse():
                          "blocks owned per rank, RCCL all-gather of 5-NN candidates per round and "
                          "all-reduce of the normal equations per LM iteration (strong scaling)")
     return ap.parse_args()
+
+
+def select_legs(args):
+    """the legs beside the headline that this run takes.  Without --full none: a plain run does
+    the headline and what its steps measure as they run, and asking it for the sharded leg is an
+    error, not a leg silently dropped.  With --full all of them, less those a --no-* option or
+    --shard-streams 0 switches off."""
+    if args.full:
+        if args.shard_streams is None:
+            args.shard_streams = 32
+        return args
+    if args.shard_streams:
+        raise SystemExit("--shard-streams sets the sharded leg, which runs only with --full")
+    args.no_cpu = args.no_exact_leg = args.no_single_stream = args.no_depth = True
+    args.shard_streams = 0
+    return args
 
 
 def drift_priors(seed, n, q_gt, t_gt):
@@ -746,6 +783,54 @@ def family_rooflines(kt, with_traffic):
     return out
 
 
+def last_step_outputs(mappers, seed):
+    """what the last solveMapping step left with the caller, for every stream of every handle
+    (handle after handle): the pose, the map <- odometry correction, the factor counts and LM
+    iterations of both outer rounds, and the published map cloud of DUMP_MAP_STREAMS streams (a
+    seeded choice, the same for the same --seed and --streams)"""
+    out = {k: [] for k in ("pose_q", "pose_t", "q_wmap_wodom", "t_wmap_wodom", "corner_num", "surf_num",
+                           "lm_iterations", "lm_final_cost")}
+    owners = []
+    for m in mappers:
+        stats = m.stats_all()
+        for b in range(m.n_streams):
+            q, t = m.pose(b)
+            _, qw, tw = m.get_state(b)
+            st = stats[b]
+            out["pose_q"].append(q)
+            out["pose_t"].append(t)
+            out["q_wmap_wodom"].append(qw)
+            out["t_wmap_wodom"].append(tw)
+            out["corner_num"].append(list(st.corner_num))
+            out["surf_num"].append(list(st.surf_num))
+            out["lm_iterations"].append([st.lm[0].iterations, st.lm[1].iterations])
+            out["lm_final_cost"].append([st.lm[0].final_cost, st.lm[1].final_cost])
+            owners.append((m, b))
+    out = {k: np.asarray(v, dtype=np.float64) for k, v in out.items()}
+    rng = np.random.default_rng(seed)
+    for g in sorted(rng.choice(len(owners), size=min(DUMP_MAP_STREAMS, len(owners)), replace=False)):
+        m, b = owners[g]
+        out[f"map_cloud_stream{g}"] = m.map_cloud(b)
+    return out
+
+
+def dump_outputs(path, outputs, seed):
+    """outputs as path/<name>.npy, float32 or float64, DUMP_LIMIT_BYTES in all: the smallest
+    arrays first, and an array that no longer fits is cut to a seeded sample of its rows, in
+    their order"""
+    os.makedirs(path, exist_ok=True)
+    left = DUMP_LIMIT_BYTES - 4096 * len(outputs)  # (the .npy headers)
+    rng = np.random.default_rng(seed + 1)
+    for name in sorted(outputs, key=lambda n: (np.asarray(outputs[n]).size, n)):
+        a = np.asarray(outputs[name])
+        a = np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
+        row = max(1, a[0].nbytes) if len(a) else 1
+        if a.nbytes > left:
+            a = a[np.sort(rng.choice(len(a), size=max(0, left // row), replace=False))]
+        left -= a.nbytes
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def aggregate(iters, dt, world, device):
     """whole-job totals: LM iterations summed over ranks, wall time = max over ranks"""
     if world <= 1:
@@ -765,7 +850,7 @@ def stream_seed(seed, rank):
 
 
 def main():
-    args = parse()
+    args = select_legs(parse())
     import torch
     import torch.distributed as dist
 
@@ -807,9 +892,9 @@ def main():
             os.dup2(saved, 1)
             os.close(saved)
 
-    def timed_run(exact):
+    def timed_run(exact, keep_outputs=False):
         """map building (untimed), then the K timed steps; returns (iterations, seconds, kernel
-        family totals, stream 0's pose after every step)"""
+        family totals, stream 0's pose after every step, last_step_outputs if asked for)"""
         if H > 1:
             # persistent LM grids sized so that every handle's fits at once: G <= CUs / all streams
             # (speed: 2 beat 4 workgroups per stream; correctness needs no residency, lm.h)
@@ -841,9 +926,10 @@ def main():
         if os.environ.get("BENCH_DEBUG_COUNTERS"):
             print(json.dumps({"debug_counters": [int(v) for v in mappers[0].debug_counters()]}), file=sys.stderr,
                   flush=True)
+        outputs = last_step_outputs(mappers, args.seed) if keep_outputs else None
         for m in mappers:
             m.close()
-        return it, secs, fam, poses
+        return it, secs, fam, poses, outputs
 
     def barrier():
         torch.cuda.synchronize(local)
@@ -851,14 +937,17 @@ def main():
             dist.barrier()
 
     plans = [[step_inputs(frames, Bh, args.stride, k, first=h * Bh) for k in range(pre + K)] for h in range(H)]
-    iters, dt, kt, poses0 = timed_run(args.exact_voxel_order)
+    iters, dt, kt, poses0, outputs = timed_run(args.exact_voxel_order, keep_outputs=bool(args.dump_outputs))
+    if outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, outputs, args.seed)
+    del outputs
     iters_all, dt_max = aggregate(iters, dt, world, f"cuda:{local}")
     if args.shard:  # every rank counted the same iterations of the same streams
         iters_all = iters_all / world
 
     exact_leg = None
     if not args.no_exact_leg and not args.shard and not args.exact_voxel_order:
-        ei, edt, ekt, eposes = timed_run(1)
+        ei, edt, ekt, eposes, _ = timed_run(1)
         ei_all, edt_max = aggregate(ei, edt, world, f"cuda:{local}")
         exact_leg = {"value": ei_all / edt_max, "ms_per_step": 1e3 * edt_max / K, "poses": eposes,
                      "kernel_ms_per_step": {k: round(v["ms"] / K, 4) for k, v in ekt.items()}}
@@ -1212,9 +1301,9 @@ def main():
                 if name == "odometry":
                     e["cpu_lm_iters_per_s"] = round(cpu_st["odometry_iters"] / (cpu_st[name] * 1e-3), 1)
             stages[name] = e
-        if world == 1 and "scan_registration" in stages:
+        if args.full and world == 1 and "scan_registration" in stages:
             stages["scan_registration"]["batched"] = scanreg_batched_stage(args.seed, local, args.n_az)
-        if world == 1 and "odometry" in stages:
+        if args.full and world == 1 and "odometry" in stages:
             stages["odometry"]["batched"] = odometry_batched_stage(frames, local)
         if not args.no_depth and world == 1:
             stages["depth_association"] = depth_stage(args.seed, local, with_cpu=not args.no_cpu)

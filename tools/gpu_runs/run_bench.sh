@@ -1,9 +1,11 @@
 #!/bin/bash
-# default bench (with cpu_baseline) + kernel-trace profile of the same command; time-limited, chained
+# full bench (with cpu_baseline and every leg) + kernel-trace profile of the headline and its GPU
+# legs; time-limited, chained.  Results go to $BENCH_OUT (default bench_out/ in the repository).
 cd "$(dirname "$0")/../.."
-mkdir -p gpurun_out
 R="$(pwd)"
-timeout -k 10 900 python bench.py > gpurun_out/bench.json 2> gpurun_out/bench.err && \
+OUT="${BENCH_OUT:-$R/bench_out}"
+mkdir -p "$OUT"
+timeout -k 10 900 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" && \
 cd /tmp && export TMPDIR=/tmp && \
-timeout -k 10 900 rocprofv3 --kernel-trace --stats -d "$R/gpurun_out/prof" -o run --output-format csv -- \
-  python3 "$R/bench.py" --no-cpu --no-single-stream > "$R/gpurun_out/prof_bench.json" 2> "$R/gpurun_out/prof_bench.err"
+timeout -k 10 900 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- \
+  python3 "$R/bench.py" --full --no-cpu --no-single-stream > "$OUT/prof_bench.json" 2> "$OUT/prof_bench.err"
