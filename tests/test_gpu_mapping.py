@@ -524,6 +524,67 @@ def test_chained_solve_matches_blocking(seq, n_streams, exact, defer_every, monk
         assert queued >= n - 2, queued  # every frame but the first ran queued behind another
 
 
+@pytest.mark.parametrize("n_streams,defer_every,feed_early", [(1, 2, False), (6, 0, False), (6, 0, True)])
+def test_saved_frame_runs_beside_newer_input(seq, n_streams, defer_every, feed_early, monkeypatch):
+    """a frame enqueued from what it saved (a deferred frame run again, 1 stream; a frame kept
+    pending behind the one in flight, 6 streams) while the streams already hold the next frame's
+    input, given but not taken: at most two frames are queued, frame f + 1 is given before frame f
+    is waited for, and the solve that takes it comes after that wait.  feed_early gives it before
+    the wait for frame f - 1 too, which is where a pending frame f is enqueued.  Every pose and
+    count equals the blocking loam_mapper_solve, bit for bit"""
+    def row(m, s):
+        st = m.stats(s)
+        q, t = m.pose(s)
+        return (q.tobytes(), t.tobytes(), st.corner_stack, st.surf_stack, tuple(st.corner_num), tuple(st.surf_num),
+                st.lm[0].iterations, st.lm[1].iterations, tuple(st.center), st.valid_num)
+
+    def feed(m, f):
+        for s in range(n_streams):
+            rec = seq[f + s]
+            m.input(s, rec["corner"], rec["surf"], rec["q_wodom"], rec["t_wodom"])
+
+    n = len(seq) - n_streams + 1
+    ref = BatchMapper(n_streams)
+    want = []
+    for f in range(n):
+        feed(ref, f)
+        ref.solve()
+        want.append([row(ref, s) for s in range(n_streams)])
+    ref.close()
+    if defer_every:
+        monkeypatch.setenv("LOAM_DEFER_EVERY", str(defer_every))
+    m = BatchMapper(n_streams)
+    monkeypatch.delenv("LOAM_DEFER_EVERY", raising=False)
+    got, rerun = [], 0
+
+    def take():  # the oldest frame in the queue
+        nonlocal rerun
+        m.wait()
+        got.append([row(m, s) for s in range(n_streams)])
+        rerun += m.stats(0).rerun
+
+    feed(m, 0)
+    m.solve_async()
+    for f in range(1, n, 2):
+        more = f + 1 < n
+        feed(m, f)
+        m.solve_async()  # behind frame f - 1: queued on the device (1 stream) or pending (6 streams)
+        if more and feed_early:
+            feed(m, f + 1)
+        take()           # frame f - 1; a pending frame f is enqueued here
+        if more and not feed_early:
+            feed(m, f + 1)
+        take()           # frame f, a deferred one run again here, with frame f + 1 given, not taken
+        if more:
+            m.solve_async()
+    if len(got) < n:
+        take()
+    m.close()
+    assert got == want
+    if defer_every:
+        assert rerun > 0, rerun
+
+
 @pytest.mark.parametrize("n_streams,exact,defer_every", [(1, 0, 0), (1, 1, 0), (3, 0, 0), (1, 0, 3), (6, 0, 0)])
 def test_solve_pose_matches_blocking(seq, n_streams, exact, defer_every, monkeypatch):
     """loam_mapper_solve_pose (include/loam_core.h): each call returns at the frame's poses, its

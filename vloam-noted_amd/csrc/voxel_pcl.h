@@ -70,7 +70,7 @@ struct VxPclOut {
   uint32_t* res_cnt = nullptr;
   uint32_t* stable_out = nullptr;
   // a block an earlier filter of the same points already allocated (the mapper's fall-back from
-  // the LDS emulation, mapper.hip): reused when the output fits it, instead of a second block
+  // the LDS emulation, mapper_map.h): reused when the output fits it, instead of a second block
   uint32_t reuse_off = 0xFFFFFFFFu, reuse_cnt = 0;
 };
 
