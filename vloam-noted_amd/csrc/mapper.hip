@@ -653,7 +653,7 @@ static int32_t mapper_create(const loam_params* p, int32_t device, int32_t n_str
     ALLOC(D.pa, B * 2 * ps);
     ALLOC(D.pb, B * 2 * ps);
     ALLOC(D.ps, B * 2 * ps);
-    ALLOC(D.pseg, B * 2 * (9 * (ps / 16) + 9));
+    ALLOC(D.pseg, B * 2 * (mp_pseg(ps) + 9));
   }
   ALLOC(D.vx_idx, B * 2 * (size_t)D.scratch_cap);
   ALLOC(D.stk_part, B * 2 * (size_t)STACK_K_MAX);

@@ -21,6 +21,26 @@ constexpr int MAP_ERR_SUBMAP = 4, MAP_ERR_EXTRA = 8, MAP_ERR_HASH = 16, MAP_ERR_
               MAP_ERR_INDEX = 64, MAP_ERR_LIVE = 128, MAP_ERR_SORT = 256,
               MAP_ERR_STACK = 512, MAP_ERR_STACK_WAIT = 2048;
 
+// Slots of MapperDev::dbg / pdbg (include/loam_core.h).  Bases of relative slots: _SEG VoxSeg::prof
+// (VXM_*, cubes) / prof_seg (VXS_*) and VxPclScratch::prof (VXP_*); _HEAP, _GLOB VxPclScratch's; _HOT, _SORT,
+// _WAVES voxel_hot.h's VHF_*, VHS_*, VHD_*; MD_LM lm.h's LmJob::prof ([-2]: the step alone).
+enum MapDbg {
+  MD_REVOX_CYC = 0 /* [3]: merge, full, append */, MD_MERGE_NEW_PTS = 3, MD_REVOX_ITEMS = 4 /* [3] */, MD_MERGES = 7,
+  MD_INDEX_CYC = 8, MD_INDEX_PTS = 9, MD_OLD_PTS = 10, MD_CUBE_SEG = 11 /* [4] */, MD_INDEX_HASH_CYC = 16,
+  MD_LM = 17 /* [7] */, MD_REVOX_SIZE_ITEMS = 24 /* [8]: by output size */, MD_REVOX_SIZE_CYC = 32 /* [8] */,
+  MD_POSE_DIFF = 40, MD_COMPACTIONS = 41, MD_STACK_SEG = 42 /* [6] */, MD_COMPACTIONS_MAP = 48 /* [2] */,
+  MD_CUBE_HOT = 50, MD_STACK_HOT = 54, MD_PREP_CYC = 58 /* [4]: FrameIn load, preparation, stack sizes, submap */,
+  MD_PREP_LAUNCHES = 62, MD_PREP_ON_DEVICE = 63, MD_CUBE_GLOB = 64, MD_STACK_GLOB = 65, MD_CUBE_HEAP = 66 /* [2] */,
+  MD_STACK_HEAP = 68 /* [2] */, MD_CUBE_SORT = 72, MD_STACK_SORT = 77, MD_CUBE_WAVES = 82, MD_STACK_CUTS = 91,
+  MD_DBG_END = 92
+};
+static_assert(MD_POSE_DIFF == 40 && MD_COMPACTIONS == 41 && MD_COMPACTIONS_MAP + 1 == 49, "slots the tests read by number");
+static_assert(MD_CUBE_HOT + VHF_SLOTS <= MD_STACK_HOT && MD_STACK_HOT + VHF_SLOTS <= MD_PREP_CYC &&
+                  MD_CUBE_SORT + VHS_SLOTS == MD_STACK_SORT && MD_STACK_SORT + VHS_SLOTS == MD_CUBE_WAVES &&
+                  MD_CUBE_WAVES + VHD_SLOTS == MD_STACK_CUTS && MD_CUBE_SEG + VXM_SLOTS <= MD_INDEX_HASH_CYC &&
+                  MD_STACK_SEG + VXS_SLOTS == MD_COMPACTIONS_MAP && MD_DBG_END <= LOAM_DEBUG_COUNTERS,
+              "counter slots");
+
 struct StreamFrame {
   double pose[7];  // in: initial guess (transformAssociateToMap); out: optimised pose
   int active;

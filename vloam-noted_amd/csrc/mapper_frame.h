@@ -181,14 +181,14 @@ __global__ void __launch_bounds__(128) k_frame_prep(MapperDev D) {
   if (!go) return;
   const unsigned long long t3 = __builtin_readcyclecounter();
   submap_prep(D, s, F);
-  if (D.pdbg && threadIdx.x == 0) {  // cycles: [58] FrameIn load, [59] device prep, [60] stack counts, [61] submap
+  if (D.pdbg && threadIdx.x == 0) {  // cycles: FrameIn load, device prep, stack counts, submap
     const unsigned long long t4 = __builtin_readcyclecounter();
-    atomicAdd(&D.pdbg[58], t1 - t0);
-    atomicAdd(&D.pdbg[59], t2 - t1);
-    atomicAdd(&D.pdbg[60], t3 - t2);
-    atomicAdd(&D.pdbg[61], t4 - t3);
-    atomicAdd(&D.pdbg[62], 1ull);
-    if (I.mode == 1) atomicAdd(&D.pdbg[63], 1ull);  // frames prepared on the device
+    atomicAdd(&D.pdbg[MD_PREP_CYC], t1 - t0);
+    atomicAdd(&D.pdbg[MD_PREP_CYC + 1], t2 - t1);
+    atomicAdd(&D.pdbg[MD_PREP_CYC + 2], t3 - t2);
+    atomicAdd(&D.pdbg[MD_PREP_CYC + 3], t4 - t3);
+    atomicAdd(&D.pdbg[MD_PREP_LAUNCHES], 1ull);
+    if (I.mode == 1) atomicAdd(&D.pdbg[MD_PREP_ON_DEVICE], 1ull);
   }
 }
 

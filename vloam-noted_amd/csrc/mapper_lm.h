@@ -85,7 +85,7 @@ __global__ void __launch_bounds__(LM_THREADS) k_lm_round(MapperDev D, int round,
   J.best_out = F.pose;
   J.err = &F.err;
   J.err_code = MAP_ERR_LM_SYNC;
-  J.prof = D.pdbg ? D.pdbg + 17 : nullptr;
+  J.prof = D.pdbg ? D.pdbg + MD_LM : nullptr;
   if (D.ipc_tab) {  // ranks in other processes: the per-pass sums meet in their mapped buffers
     J.rank = D.rank;
     J.nrank = D.nrank;
@@ -152,7 +152,7 @@ __global__ void __launch_bounds__(LM_THREADS) k_lm_group(LmGroupArgs A, int roun
   J.best_out = F.pose;
   J.err = &F.err;
   J.err_code = MAP_ERR_LM_SYNC;
-  J.prof = a.pdbg ? a.pdbg + 17 : nullptr;
+  J.prof = a.pdbg ? a.pdbg + MD_LM : nullptr;
   J.rank = rank;
   J.nrank = R;
   const size_t sr = (size_t)s * 2 + round;
@@ -189,7 +189,7 @@ __global__ void k_pose_adopt(MapperDev D) {
   StreamFrame& F = D.fr[s];
   if (i < 7) {
     const double v = D.pose_x[(size_t)s * 8 + i];  // rank 0's slot
-    if (__double_as_longlong(v) != __double_as_longlong(F.pose[i])) atomicAdd(&D.dbg[40], 1ull);
+    if (__double_as_longlong(v) != __double_as_longlong(F.pose[i])) atomicAdd(&D.dbg[MD_POSE_DIFF], 1ull);
     F.pose[i] = v;
   }
 }

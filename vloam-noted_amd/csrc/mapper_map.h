@@ -222,7 +222,6 @@ __global__ void __launch_bounds__(VX_THREADS) k_insert_bucket(MapperDev D) {
 #endif
 template <bool PCL>
 __device__ inline void revox_item(MapperDev& D, int s, int m, int slot, int cube, int append, uint32_t* lds) {
-  constexpr int LW = VX_LDS_WORDS;
   StreamFrame& F = D.fr[s];
   const uint32_t* ioff = D.ins_off + sm_index(s, m) * (INS_SLOTS + 1);
   const uint32_t i0 = ioff[slot], n_new = ioff[slot + 1] - i0;
@@ -251,65 +250,23 @@ __device__ inline void revox_item(MapperDev& D, int s, int m, int slot, int cube
   S.scratch_tail = &F.scratch_tail[m];
   S.scratch_cap = D.scratch_cap;
   S.err = &F.err;
-  S.prof = D.pdbg ? D.pdbg + 11 : nullptr;  // merge phases: dbg[11..14]
+  S.prof = D.pdbg ? D.pdbg + MD_CUBE_SEG : nullptr;  // merge phases
   S.anchored = 1;  // a merge keys the voxels from the cube's corner (VoxSeg::anchored)
   cube_corner(cube, F.cen, S.anchor);
   bool merged = false;
   const unsigned long long t0 = __builtin_readcyclecounter();
   const bool fixed = n_new > 0 && n_new <= VX_MERGE_CAP && cv.y > 0 && *tok == cv.x + 1;
   if (PCL && !append) {
-    // PCL's summation order (exact_voxel_order): also a window cube that received nothing but
-    // is not a VoxelGrid fixed point (raw appended content, content set through the API), as the
-    // reference re-filters every window cube (:795-808)
-    uint32_t* sb = lds + LW - 3;
-    const uint32_t n = cv.y + n_new;
-    if (threadIdx.x == 0) *sb = atomicAdd(&F.hot_tail[m], n + MP_SLACK);
+    // PCL's summation order (exact_voxel_order): also a window cube that received nothing but is not a
+    // VoxelGrid fixed point (raw appended or API-set content; the reference re-filters every window
+    // cube, :795-808).  Its block of the sort scratch first
+    uint32_t* sb = vx_park_block(lds);
+    if (threadIdx.x == 0) *sb = atomicAdd(&F.hot_tail[m], cv.y + n_new + MP_SLACK);
     __syncthreads();
     const uint32_t so = *sb;
     __syncthreads();
-    bool global = n > (uint32_t)VH_BIG_N;
-    uint32_t reuse_off = 0xFFFFFFFFu, reuse_cnt = 0;
-    if (!global) {
-      // the input-order filter sums every voxel of at most 2 members (order-free) and records the
-      // others, then voxel_hot.h sums those in std::sort's order
-      if ((size_t)so + n + MP_SLACK > mp_cube_scratch(D)) {
-        if (threadIdx.x == 0) atomicOr(&F.err, MAP_ERR_SORT);
-      } else {
-        S.hot = map_hot(D, sm_index(s, m), so, n);
-        if (fixed) {
-          merged = vx_merge_fixed_point<VX_THREADS, (int)VX_MERGE_CAP, VX_LDS_WORDS, true>(S, lds);
-          __syncthreads();  // false: grid overflow, full filter below
-        }
-        if (!merged) voxel_segment(S, lds);
-        const VxSrc P{ar + cv.x, (int)cv.y, D.ins_sorted + sm_index(s, m) * D.max_in + i0};
-        const int he = vh_fixup<VX_THREADS>(P, (int)n, ar, S.hot, lds, LW - 256, *reinterpret_cast<VxMisc*>(lds + LW - 192),
-                                            tok, &F.err, D.pdbg ? D.pdbg + 50 : nullptr,
-                                            D.pdbg ? D.pdbg + 72 : nullptr, D.pdbg ? D.pdbg + 82 : nullptr);
-        // (over VH_MAX_N, a part too large for the LDS after the first partition: the global
-        // sort below writes the cube again, into the block the filter above allocated for it:
-        // the same voxels, so the same count)
-        global = he < 0;
-        __syncthreads();
-        if (global) {
-          const uint2 v = tab[cube];  // (thread 0 wrote it inside the filter, before the barrier)
-          reuse_off = v.x;
-          reuse_cnt = v.y;
-        }
-      }
-    }
-    if (global) {  // the whole std::sort emulated in global memory (voxel_pcl.h)
-      VxPclOut O;
-      O.reuse_off = reuse_off;
-      O.reuse_cnt = reuse_cnt;
-      O.out = ar;
-      O.tail = &F.arena_tail[m];
-      O.cap = D.map_cap;
-      O.res_off = &tab[cube].x;
-      O.res_cnt = &tab[cube].y;
-      O.stable_out = tok;
-      map_voxel_pcl(D, sm_index(s, m), so, VxSrc{ar + cv.x, (int)cv.y, D.ins_sorted + sm_index(s, m) * D.max_in + i0},
-                    (int)n, D.leaf[m], O, lds, &F.err);
-    }
+    S.hot = map_hot(D, sm_index(s, m), so, cv.y + n_new);
+    map_filter_exact(D, sm_index(s, m), so, S, VxSrc{S.src0, S.n0, S.src1}, lds, &tab[cube], fixed, &merged);
     __syncthreads();
   } else {
     if (!append && fixed) {
@@ -321,7 +278,7 @@ __device__ inline void revox_item(MapperDev& D, int s, int m, int slot, int cube
   }
   const unsigned long long t1 = __builtin_readcyclecounter();
   // the cube's new content -> its cell index (cubeindex.h)
-  uint32_t* res = lds + LW - 2;
+  uint32_t* res = vx_park_result(lds);
   if (threadIdx.x == 0) {
     const uint2 v = tab[cube];  // written by this thread inside the filter
     res[0] = v.x;
@@ -333,7 +290,7 @@ __device__ inline void revox_item(MapperDev& D, int s, int m, int slot, int cube
   int corner[3];
   cube_corner(cube, F.cen, corner);
   if (!cube_index_build<VX_THREADS, CI_LDS_MAX_T>(ar + off, n, corner, carena_base(D, s, m, F.arena_active[m]) + off,
-                                  ctab_base(D, s, m, F.arena_active[m]) + 4 * (size_t)off, lds, D.pdbg ? D.pdbg + 16 : nullptr) &&
+                                  ctab_base(D, s, m, F.arena_active[m]) + 4 * (size_t)off, lds, D.pdbg ? D.pdbg + MD_INDEX_HASH_CYC : nullptr) &&
       threadIdx.x == 0)
     atomicOr(&F.err, MAP_ERR_INDEX);
   // read old content + new points, write the filtered cube, then its index (read it, write
@@ -343,18 +300,18 @@ __device__ inline void revox_item(MapperDev& D, int s, int m, int slot, int cube
   if (threadIdx.x == 0 && D.pdbg) {
     const unsigned long long t2 = __builtin_readcyclecounter();
     const int k = merged ? 0 : (append ? 2 : 1);
-    atomicAdd(&D.dbg[k], t1 - t0);       // filter cycles: merge / full / append
-    atomicAdd(&D.dbg[4 + k], 1ull);      // items
-    atomicAdd(&D.dbg[8], t2 - t1);       // index build cycles
-    atomicAdd(&D.dbg[9], (unsigned long long)n);
-    atomicAdd(&D.dbg[10], (unsigned long long)cv.y);
+    atomicAdd(&D.dbg[MD_REVOX_CYC + k], t1 - t0);  // filter cycles: merge / full / append
+    atomicAdd(&D.dbg[MD_REVOX_ITEMS + k], 1ull);
+    atomicAdd(&D.dbg[MD_INDEX_CYC], t2 - t1);
+    atomicAdd(&D.dbg[MD_INDEX_PTS], (unsigned long long)n);
+    atomicAdd(&D.dbg[MD_OLD_PTS], (unsigned long long)cv.y);
     int hb = 0;
     while (hb < 7 && n >= (1024u << hb)) ++hb;
-    atomicAdd(&D.dbg[24 + hb], 1ull);
-    atomicAdd(&D.dbg[32 + hb], t2 - t0);
+    atomicAdd(&D.dbg[MD_REVOX_SIZE_ITEMS + hb], 1ull);
+    atomicAdd(&D.dbg[MD_REVOX_SIZE_CYC + hb], t2 - t0);
     if (merged) {
-      atomicAdd(&D.dbg[3], (unsigned long long)n_new);  // new points of merged cubes
-      atomicAdd(&D.dbg[7], 1ull);                       // merges
+      atomicAdd(&D.dbg[MD_MERGE_NEW_PTS], (unsigned long long)n_new);
+      atomicAdd(&D.dbg[MD_MERGES], 1ull);
     }
   }
 }
@@ -486,8 +443,8 @@ __global__ void k_compact_commit(MapperDev D, const uint32_t* new_off) {
     F.arena_tail[m] = no[NCUBE];
     F.arena_active[m] = 1 - F.arena_active[m];
     if (no[NCUBE] > D.compact_at) atomicOr(&F.err, MAP_ERR_LIVE);  // the live map itself
-    atomicAdd(&D.dbg[41], 1ull);
-    atomicAdd(&D.dbg[48 + m], 1ull);  // per map
+    atomicAdd(&D.dbg[MD_COMPACTIONS], 1ull);
+    atomicAdd(&D.dbg[MD_COMPACTIONS_MAP + m], 1ull);
   }
 }
 

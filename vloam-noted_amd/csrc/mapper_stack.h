@@ -12,63 +12,57 @@ namespace loam {
 constexpr int MP_LDS_N = 8192;                                    // E 64 KiB + A, B 32 KiB each
 constexpr int MP_LEV_W = 40;  // SsLevels words
 static_assert(sizeof(SsLevels) <= 4 * MP_LEV_W, "SsLevels area");
-constexpr int MP_SEG_LDS = (VX_LDS_WORDS - 256 - 2 * MP_LEV_W - 4 * MP_LDS_N) / 6;  // level lists beside them
+constexpr int MP_SEG_LDS = (VX_LDS_WORDS - VX_TAIL_WORDS - 2 * MP_LEV_W - 4 * MP_LDS_N) / 6;  // level lists beside them
 static_assert(MP_SEG_LDS >= MP_LDS_N / (SS_THRESHOLD + 1) + 2, "level lists of an LDS-resident sort");
-static_assert(VX_THREADS / 64 * SS_LOC_WORDS + 256 + 2 * MP_LEV_W <= VX_LDS_WORDS, "wave-local sort buffers");
+static_assert(VX_THREADS / 64 * SS_LOC_WORDS + VX_TAIL_WORDS + 2 * MP_LEV_W <= VX_LDS_WORDS, "wave-local sort buffers");
 // global-memory sorts: segments of at most MP_LDS_N elements are sorted whole in LDS
 // (ss_sort_deferred: E, A, B and the level lists of one segment at a time)
 constexpr int MP_DEF_SEG = MP_LDS_N / (SS_THRESHOLD + 1) + 2;
-static_assert(4 * MP_LDS_N + 6 * MP_DEF_SEG + 256 + 2 * MP_LEV_W <= VX_LDS_WORDS, "deferred segment sort in LDS");
-// sort scratch of a (stream, map): the stack at 0, the cubes' blocks of n + MP_SLACK from the
-// frame's scratch_tail; the level lists and the deferred list of a global-memory sort at
-// 9 (offset / 16) ints
+static_assert(4 * MP_LDS_N + 6 * MP_DEF_SEG + VX_TAIL_WORDS + 2 * MP_LEV_W <= VX_LDS_WORDS, "deferred segment sort in LDS");
+// sort scratch of a (stream, map), mp_scratch elements: the cubes' blocks of n + MP_SLACK from 0
+// (the frame's hot_tail), below the stack's (its own region: it may run beside the previous
+// frame's re-filter) at mp_stack_offset
 constexpr uint32_t MP_SLACK = 64;
-// cubes from 0, the stack (its own region: it may run beside the previous frame's re-filter)
-// at mp_stack_offset
-__host__ __device__ inline size_t mp_cube_scratch(const MapperDev& D) {
-  return (size_t)D.scratch_cap + MP_SLACK * (INS_SLOTS + 1);
-}
+__host__ __device__ inline size_t mp_cube_scratch(const MapperDev& D) { return (size_t)D.scratch_cap + MP_SLACK * (INS_SLOTS + 1); }
 __host__ __device__ inline uint32_t mp_stack_offset(const MapperDev& D) { return (uint32_t)mp_cube_scratch(D); }
-inline size_t mp_scratch(const MapperDev& D) { return mp_cube_scratch(D) + (size_t)D.max_in + MP_SLACK; }
+__host__ __device__ inline size_t mp_scratch(const MapperDev& D) { return mp_cube_scratch(D) + (size_t)D.max_in + MP_SLACK; }
+// D.pseg (a global-memory sort's level and deferred lists): the ints before element offset off of
+// the sort scratch, 9 per 16 elements; a (stream, map) has mp_pseg(ps) + 9
+template <typename T>
+__host__ __device__ inline T mp_pseg(T off) { return 9 * (off / 16); }
 template <typename PF>
 __device__ inline bool map_voxel_pcl(const MapperDev& D, size_t sm, uint32_t so, const PF& P, int n, float leaf,
                                      const VxPclOut& O, uint32_t* lds, int* err) {
-  const size_t ps = (size_t)D.scratch_cap + MP_SLACK * (INS_SLOTS + 1) + (size_t)D.max_in + MP_SLACK;
+  const size_t ps = mp_scratch(D);
   const bool stk = so == mp_stack_offset(D);
   const size_t lim = stk ? ps : mp_cube_scratch(D);  // cubes stay below the stack
   if ((size_t)so + (uint32_t)n + MP_SLACK > lim) {
     if (threadIdx.x == 0) atomicOr(err, MAP_ERR_SORT);
     return false;
   }
-  VxMisc& M = *reinterpret_cast<VxMisc*>(lds + VX_LDS_WORDS - 192);
-  uint32_t* ws = lds + VX_LDS_WORDS - 256;
-  SsLevels* lev = reinterpret_cast<SsLevels*>(lds + VX_LDS_WORDS - 256 - MP_LEV_W);
+  VxMisc& M = vx_misc(lds);
+  uint32_t* ws = vx_ws(lds);
+  SsLevels* lev = reinterpret_cast<SsLevels*>(lds + VX_LDS_WORDS - VX_TAIL_WORDS - MP_LEV_W);
   const size_t b = sm * ps + so;
+  // the counters of the stack's or the cubes' sorts
+  auto slot = [&](int stack, int cube) { return D.pdbg ? (stk ? D.pdbg + stack : D.pdbg + cube) : nullptr; };
+  unsigned long long *prof = slot(MD_STACK_SEG, MD_CUBE_SEG), *heap = slot(MD_STACK_HEAP, MD_CUBE_HEAP),
+                     *glob = slot(MD_STACK_GLOB, MD_CUBE_GLOB);
   if (n <= MP_LDS_N) {
     uint64_t* E = reinterpret_cast<uint64_t*>(lds);
     uint32_t* A = lds + 2 * MP_LDS_N;
     uint32_t* B = A + MP_LDS_N;
     int* seg0 = reinterpret_cast<int*>(B + MP_LDS_N);
-    const VxPclScratch X{E, A, B, D.ps + b, lev, {seg0, seg0 + 3 * MP_SEG_LDS}, MP_SEG_LDS, nullptr,
-                         D.pdbg ? (stk ? D.pdbg + 42 : D.pdbg + 11) : nullptr, D.pdbg ? (stk ? D.pdbg + 68 : D.pdbg + 66) : nullptr,
-                         D.pdbg ? (stk ? D.pdbg + 65 : D.pdbg + 64) : nullptr};
+    const VxPclScratch X{E, A, B, D.ps + b, lev, {seg0, seg0 + 3 * MP_SEG_LDS}, MP_SEG_LDS, nullptr, prof, heap, glob};
     voxel_grid_pcl<VX_THREADS>(P, n, leaf, O, X, M, ws, err);
   } else {  // level lists in global memory; segments that fit the LDS are sorted there whole
     const int cap = (int)((n + MP_SLACK) / 16);
-    int* seg0 = D.pseg + sm * (9 * (ps / 16) + 9) + 9 * (so / 16);
-    const VxPclDefer dfr{MP_LDS_N,
-                         seg0 + 6 * cap,
-                         cap,
-                         reinterpret_cast<uint64_t*>(lds),
-                         lds + 2 * MP_LDS_N,
-                         lds + 3 * MP_LDS_N,
-                         reinterpret_cast<int*>(lds + 4 * MP_LDS_N),
-                         reinterpret_cast<int*>(lds + 4 * MP_LDS_N) + 3 * MP_DEF_SEG,
-                         MP_DEF_SEG,
-                         reinterpret_cast<SsLevels*>(lds + VX_LDS_WORDS - 256 - 2 * MP_LEV_W)};
-    const VxPclScratch X{D.pe + b, D.pa + b, D.pb + b, D.ps + b, lev, {seg0, seg0 + 3 * cap}, cap, lds,
-                         D.pdbg ? (stk ? D.pdbg + 42 : D.pdbg + 11) : nullptr, D.pdbg ? (stk ? D.pdbg + 68 : D.pdbg + 66) : nullptr,
-                         D.pdbg ? (stk ? D.pdbg + 65 : D.pdbg + 64) : nullptr};
+    int* seg0 = D.pseg + sm * (mp_pseg(ps) + 9) + mp_pseg(so);
+    int* dseg = reinterpret_cast<int*>(lds + 4 * MP_LDS_N);
+    const VxPclDefer dfr{MP_LDS_N, seg0 + 6 * cap, cap, reinterpret_cast<uint64_t*>(lds), lds + 2 * MP_LDS_N,
+                         lds + 3 * MP_LDS_N, dseg, dseg + 3 * MP_DEF_SEG, MP_DEF_SEG,
+                         reinterpret_cast<SsLevels*>(lds + VX_LDS_WORDS - VX_TAIL_WORDS - 2 * MP_LEV_W)};
+    const VxPclScratch X{D.pe + b, D.pa + b, D.pb + b, D.ps + b, lev, {seg0, seg0 + 3 * cap}, cap, lds, prof, heap, glob};
     voxel_grid_pcl<VX_THREADS, true>(P, n, leaf, O, X, M, ws, err, &dfr);
   }
   return true;
@@ -78,15 +72,43 @@ __device__ inline bool map_voxel_pcl(const MapperDev& D, size_t sm, uint32_t so,
 // scratch at offset so (a block of n + MP_SLACK): rk in pa, fpos in pb, the member lists and the
 // per-voxel records in pe (2 (n + MP_SLACK) words)
 __device__ inline VxHot map_hot(const MapperDev& D, size_t sm, uint32_t so, uint32_t n) {
-  const size_t b = sm * (mp_cube_scratch(D) + (size_t)D.max_in + MP_SLACK) + so;
-  VxHot H;
-  H.rk = D.pa + b;
-  H.fpos = D.pb + b;
-  H.hl = reinterpret_cast<uint32_t*>(D.pe + b);
-  H.hv = H.hl + n;
-  H.cap_h = n / 3 + 1;
-  H.w = D.ps + b;  // (sorts of VH_MAX_N .. VH_BIG_N points: vh_sort_big)
-  return H;
+  const size_t b = sm * mp_scratch(D) + so;
+  uint32_t* hl = reinterpret_cast<uint32_t*>(D.pe + b);
+  return VxHot{D.pa + b, hl, hl + n, D.pb + b, n / 3 + 1, D.ps + b};  // (w: sorts of VH_MAX_N .. VH_BIG_N points)
+}
+
+__device__ inline VxPclOut map_pcl_out(const VoxSeg& S, uint32_t reuse_off, uint32_t reuse_cnt) {
+  return VxPclOut{S.out, S.tail, S.cap, S.res_off, S.res_cnt, S.stable_out, reuse_off, reuse_cnt};
+}
+// The exact-order ladder of the filter S (S.src1 used whole; S.hot = map_hot of its sort-scratch
+// block at offset so) of a (stream, map): up to VH_BIG_N points vx_filter_exact (the merge when
+// `fixed`; merged: it ran); above, or when vh_fixup cannot split the sort for the LDS (he < 0), the
+// whole std::sort in global memory on the points P.  entry: a cube's table entry (the stack: null).
+template <typename PF>
+__device__ __attribute__((always_inline)) inline void map_filter_exact(
+    const MapperDev& D, size_t sm, uint32_t so, const VoxSeg& S, const PF& P, uint32_t* lds,
+    const uint2* entry = nullptr, bool fixed = false, bool* merged = nullptr) {
+  const uint32_t n = (uint32_t)(S.n0 + S.n1);
+  bool global = n > (uint32_t)VH_BIG_N;
+  uint32_t reuse_off = 0xFFFFFFFFu, reuse_cnt = 0;
+  if (!global) {
+    if (entry && (size_t)so + n + MP_SLACK > mp_cube_scratch(D)) {
+      if (threadIdx.x == 0) atomicOr(S.err, MAP_ERR_SORT);  // (only cubes: the stack's block holds max_in)
+    } else {
+      auto slot = [&](int stack, int cube) { return D.pdbg ? D.pdbg + (entry ? cube : stack) : nullptr; };
+      const VhDiag C{slot(MD_STACK_HOT, MD_CUBE_HOT), slot(MD_STACK_SORT, MD_CUBE_SORT),
+                     entry && D.pdbg ? D.pdbg + MD_CUBE_WAVES : nullptr};
+      int he;
+      if constexpr (std::is_same<PF, VxSrc>::value) he = vx_filter_exact<VX_THREADS>(S, P, (int)n, lds, S.stable_out, S.err, C, fixed, merged);
+      else he = vx_filter_exact<VX_THREADS>(S, VxSrc{S.src0, S.n0, S.src1}, (int)n, lds, S.stable_out, S.err, C, fixed, merged);
+      global = he < 0;
+      __syncthreads();
+      // the global sort writes a cube again, into the block the filter allocated (the entry, written before
+      // the barrier).  Also after VX_ERR_OUTPUT, when the entry is the old content's: that fix is a change of its own
+      if (global && entry) reuse_off = entry->x, reuse_cnt = entry->y;
+    }
+  }
+  if (global) map_voxel_pcl(D, sm, so, P, (int)n, S.leaf, map_pcl_out(S, reuse_off, reuse_cnt), lds, S.err);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -101,22 +123,10 @@ __global__ void __launch_bounds__(VX_THREADS) k_stack_ds(MapperDev D) {
   if (!I.active) return;
   const size_t sm = sm_index(s, m);
   int* err = &D.stk_err[s];
-  // PCL's order above VH_BIG_N points (or when vh_fixup cannot split the sort for the LDS): the
-  // whole sort in global memory
-  bool global = PCL && I.n[m] > VH_BIG_N;
-  if (!global) {
-  VoxSeg S;
-  S.src1 = nullptr;
-  S.tag1 = nullptr;
-  S.n1 = 0;
-  S.tag = 0;
+  VoxSeg S{};  // (no secondary source, tail or offset word)
   S.leaf = D.leaf[m];
-  S.append_only = 0;
-  S.tail = nullptr;
-  S.res_off = nullptr;
-  S.scratch_tail = nullptr;
   S.err = err;
-  S.prof_seg = D.pdbg ? D.pdbg + 42 : nullptr;  // stack VoxelGrid phases: dbg[42..45]
+  S.prof_seg = D.pdbg ? D.pdbg + MD_STACK_SEG : nullptr;  // stack VoxelGrid phases
   S.src0 = I.p[m];
   S.n0 = I.n[m];
   S.out = D.stack[m] + (size_t)s * D.max_in;
@@ -125,23 +135,9 @@ __global__ void __launch_bounds__(VX_THREADS) k_stack_ds(MapperDev D) {
   S.scratch_pts = D.stk_pts + sm * D.max_in;
   S.scratch_idx = D.stk_idx + sm * D.max_in;
   S.scratch_cap = D.max_in;
-  if (PCL) S.hot = map_hot(D, sm, mp_stack_offset(D), (uint32_t)I.n[m]);
-  voxel_segment(S, lds);
-  if (PCL) {  // PCL's summation order for the voxels of 3+ members (voxel_hot.h)
-    const int he = vh_fixup<VX_THREADS>(VxSrc{I.p[m], I.n[m], nullptr}, I.n[m], S.out, S.hot, lds, VX_LDS_WORDS - 256,
-                                        *reinterpret_cast<VxMisc*>(lds + VX_LDS_WORDS - 192), nullptr, err,
-                                        D.pdbg ? D.pdbg + 54 : nullptr, D.pdbg ? D.pdbg + 77 : nullptr);
-    global = he < 0;  // (over VH_MAX_N: the first partition left a part too large for the LDS)
-    __syncthreads();
-  }
-  }
-  if (PCL && global) {
-    VxPclOut O;
-    O.out = D.stack[m] + (size_t)s * D.max_in;
-    O.cap = D.max_in;
-    O.res_cnt = reinterpret_cast<uint32_t*>(&D.stk_n[2 * s + m]);
-    map_voxel_pcl(D, sm, mp_stack_offset(D), VxPtrSrc{I.p[m]}, I.n[m], D.leaf[m], O, lds, err);
-  }
+  if (PCL) S.hot = map_hot(D, sm, mp_stack_offset(D), (uint32_t)I.n[m]);  // PCL's summation order
+  if (PCL) map_filter_exact(D, sm, mp_stack_offset(D), S, VxPtrSrc{I.p[m]}, lds);
+  else voxel_segment(S, lds);
 }
 
 // Few streams: the input-order stack VoxelGrid of a (stream, map) over stack_k workgroups.
@@ -164,8 +160,8 @@ __global__ void __launch_bounds__(VX_THREADS) k_stack_part(MapperDev D) {
   const uint32_t N = (uint32_t)I.n[m];
   const VxSrc P{I.p[m], (int)N, nullptr};
   float4* stage = D.stk_pts + sm * D.max_in;
-  uint32_t* ws = lds + VX_LDS_WORDS - 256;
-  VxMisc& M = *reinterpret_cast<VxMisc*>(lds + VX_LDS_WORDS - 192);
+  uint32_t* ws = vx_ws(lds);
+  VxMisc& M = vx_misc(lds);
   const int tid = threadIdx.x;
   if (N == 0) {
     if (tid == 0) part[j] = make_uint2(0, 0);
@@ -173,7 +169,7 @@ __global__ void __launch_bounds__(VX_THREADS) k_stack_part(MapperDev D) {
   }
   unsigned long long tp = __builtin_readcyclecounter();  // phase counters (diagnostics)
   vx_geometry(P, N, D.leaf[m], M);
-  vx_phase(D.pdbg ? D.pdbg + 42 : nullptr, 0, &tp);  // bounding box -> dbg[42] (summed over the K parts)
+  vx_phase(D.pdbg ? D.pdbg + MD_STACK_SEG : nullptr, 0, &tp);  // bounding box (summed over the K parts)
   const VxGeom g = M.g;
   if (g.overflow) {  // PCL: "Leaf size is too small" -> output = input (range 0 copies it)
     if (j == 0)
@@ -241,35 +237,25 @@ __global__ void __launch_bounds__(VX_THREADS) k_stack_part(MapperDev D) {
   __syncthreads();
   const uint32_t b0 = M.sbase[0], b1 = max(M.sbase[0], M.sbase[1]), base = (uint32_t)M.sfail;
   __syncthreads();  // vx_group reuses M
-  vx_phase(D.pdbg ? D.pdbg + 91 : nullptr, 0, &tp);  // histogram + range cuts -> dbg[91]
+  vx_phase(D.pdbg ? D.pdbg + MD_STACK_CUTS : nullptr, 0, &tp);  // histogram + range cuts
   if (b0 >= b1) {  // empty range
     if (tid == 0) part[j] = make_uint2(base, 0);
     return;
   }
-  VoxSeg S;
+  VoxSeg S{};  // (no secondary source, tail or result words)
   S.src0 = I.p[m];
   S.n0 = (int)N;
-  S.src1 = nullptr;
-  S.tag1 = nullptr;
-  S.n1 = 0;
-  S.tag = 0;
   S.leaf = D.leaf[m];
-  S.append_only = 0;
   S.out = stage;
-  S.tail = nullptr;
   S.cap = (uint32_t)D.max_in;
-  S.res_off = nullptr;
-  S.res_cnt = nullptr;
-  S.scratch_pts = nullptr;
   S.scratch_idx = D.stk_idx + sm * D.max_in;
-  S.scratch_tail = nullptr;
   S.scratch_cap = (uint32_t)D.max_in;
   S.err = &D.stk_err[s];
-  S.prof_seg = D.pdbg ? D.pdbg + 42 : nullptr;  // hash, sort + scan, members + centroids -> dbg[43..45]
+  S.prof_seg = D.pdbg ? D.pdbg + MD_STACK_SEG : nullptr;  // hash, sort + scan, members + centroids
   int moved = 0;
   const uint32_t klo = blo(b0), khi = b1 >= (uint32_t)VX_NB ? 0xFFFFFFFFu : blo(b1);
   const uint32_t U = vx_group(S, g, P, N, D.stk_idx + sm * D.max_in + base, klo, khi, base,
-                              VX_LDS_WORDS - 256, lds, ws, M, &moved);
+                              VX_LDS_WORDS - VX_TAIL_WORDS, lds, ws, M, &moved);
   if (tid == 0) {
     if (U == VX_OVERFLOW) atomicOr(&D.stk_err[s], MAP_ERR_STACK);
     part[j] = make_uint2(base, U == VX_OVERFLOW ? 0u : U);

@@ -88,14 +88,11 @@ __global__ void __launch_bounds__(P_PCL_THREADS) k_voxel_pcl_one(const float4* s
   voxel_grid_pcl<P_PCL_THREADS>(VxPtrSrc{src}, n, leaf, O, X, M, ws, err);
 }
 
-// PCL-order VoxelGrid of one cloud of at most VH_MAX_N points the way the mapper runs it
-// (exact_voxel_order): the input-order filter for the voxels of at most 2 members, the pruned
-// std::sort emulation for the others (voxel_hot.h)
+// PCL-order VoxelGrid of one cloud of at most VH_MAX_N points with the mapper's and scan
+// registration's own driver (exact_voxel_order; voxel_hot.h vx_filter_exact)
 __global__ void __launch_bounds__(VX_THREADS) k_voxel_hot_one(VoxSeg S, int* err) {
   __shared__ __attribute__((aligned(16))) uint32_t lds[VX_LDS_WORDS];
-  voxel_segment(S, lds);
-  vh_fixup<VX_THREADS>(VxSrc{S.src0, S.n0, nullptr}, S.n0, S.out, S.hot, lds, VX_LDS_WORDS - 256,
-                       *reinterpret_cast<VxMisc*>(lds + VX_LDS_WORDS - 192), nullptr, err);
+  vx_filter_exact<VX_THREADS>(S, VxSrc{S.src0, S.n0, nullptr}, S.n0, lds, nullptr, err);
 }
 
 struct PKeyLess {
@@ -412,11 +409,7 @@ int32_t loam_voxel_grid_pcl(int32_t device, const float* in, int32_t n, float le
     S.scratch_idx = (int*)didx.p;
     S.scratch_cap = (uint32_t)m;
     S.err = (int*)derr.p;
-    S.hot.rk = (uint32_t*)drk.p;
-    S.hot.hl = (uint32_t*)dhl.p;
-    S.hot.hv = (uint32_t*)dhv.p;
-    S.hot.fpos = (uint32_t*)dfp.p;
-    S.hot.cap_h = (uint32_t)(n / 3 + 1);
+    S.hot = VxHot{(uint32_t*)drk.p, (uint32_t*)dhl.p, (uint32_t*)dhv.p, (uint32_t*)dfp.p, (uint32_t)(n / 3 + 1)};
     k_voxel_hot_one<<<1, VX_THREADS>>>(S, (int*)derr.p);
     LOAM_HIP(hipGetLastError());
     uint32_t cnt = 0;

@@ -94,6 +94,14 @@ struct SrDev {
   unsigned long long* dbg;  // [LOAM_SR_DEBUG_COUNTERS] (loam_scanreg_debug_counters)
   unsigned long long* pdbg;  // dbg when LOAM_PHASE_COUNTERS=1 at create, else null (no cycle counting)
 };
+// the counters' slots (include/loam_core.h); SR_VOX_HOT / _SORT: bases of voxel_hot.h's VHF_* / VHS_*
+enum SrDbg {
+  SR_VOX_HOT = 0, SR_VOX_MAX_CYC = 3, SR_VOX_SEG_CYC, SR_VOX_PTS, SR_VOX_MAX_PTS, SR_VOX_MAX_HEAP, SR_VOX_SORT,
+  SR_SEL_SORT_CYC = 13, SR_SEL_GREEDY_CYC, SR_SEL_MAX_CYC, SR_VOX_SLOWEST, SR_VOX_SLOWEST_FIX = 18, SR_SEL_MAX_SORT,
+  SR_SEL_MAX_GREEDY, SR_SECTOR_RERUNS, SR_RINGS_CONCURRENT, SR_DBG_END
+};
+static_assert(SR_VOX_HOT + VHF_SLOTS <= SR_VOX_MAX_CYC && SR_VOX_SORT + VHS_SLOTS <= SR_SEL_SORT_CYC &&
+                  SR_DBG_END <= LOAM_SR_DEBUG_COUNTERS, "scan registration counter slots");
 
 // scan_registration.cpp:217-259 (float atan/sqrt like the reference's float overloads)
 __device__ inline int sr_scan_id(float x, float y, float z, int n_scans) {
@@ -633,7 +641,7 @@ __device__ inline void sr_greedy_ring(int base, const int* lo, const int* hi, co
       __builtin_amdgcn_wave_barrier();
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
       sr_greedy_sector(base, lo[j], hi[j], true, keys + j * SR_WSORT_MAX, len[j], picked, lab, gapok, sect[j]);
-      if (lane == 0 && dbg) atomicAdd(dbg + 21, 1ull);  // (debug counter 21: sector reruns)
+      if (lane == 0 && dbg) atomicAdd(dbg + SR_SECTOR_RERUNS, 1ull);
     }
   }
   __syncthreads();
@@ -732,7 +740,7 @@ __device__ inline int sr_select_ring(const SrDev& D, int r, const SrSelLds& M) {
     minlen = min(minlen, len[j]);
   }
   const bool fast = maxlen <= SR_WSORT_MAX;
-  unsigned long long* prof = D.pdbg;  // (diagnostics: [13] sector sorts, [14] greedy, [15] slowest ring)
+  unsigned long long* prof = D.pdbg;  // (diagnostics: SR_SEL_*)
   const unsigned long long t0 = prof ? __builtin_readcyclecounter() : 0ull;
   if (!fast && maxlen > 6 * SR_WSORT_MAX) {
     if (tid == 0) {
@@ -753,7 +761,7 @@ __device__ inline int sr_select_ring(const SrDev& D, int r, const SrSelLds& M) {
   const unsigned long long t1 = prof ? __builtin_readcyclecounter() : 0ull;
   if (fast && minlen >= SR_CONC_MIN) {
     sr_greedy_ring(base, lo, hi, keys, len, picked, lab, M.gapok, M.sect, D.dbg);
-    if (tid == 0 && D.dbg) atomicAdd(D.dbg + 22, 1ull);  // (debug counter 22: rings with concurrent sectors)
+    if (tid == 0 && D.dbg) atomicAdd(D.dbg + SR_RINGS_CONCURRENT, 1ull);
   } else {
     // sequential sectors (a ring with a sector over SR_WSORT_MAX points, or one shorter than
     // SR_CONC_MIN): every suppression flag written where the reference writes it
@@ -795,11 +803,11 @@ __device__ inline int sr_select_ring(const SrDev& D, int r, const SrSelLds& M) {
   }
   if (prof && tid == 0) {
     const unsigned long long t2 = __builtin_readcyclecounter();
-    atomicAdd(prof + 13, t1 - t0);
-    atomicAdd(prof + 14, t2 - t1);
-    atomicMax(prof + 15, t2 - t0);
-    atomicMax(prof + 19, t1 - t0);
-    atomicMax(prof + 20, t2 - t1);
+    atomicAdd(prof + SR_SEL_SORT_CYC, t1 - t0);
+    atomicAdd(prof + SR_SEL_GREEDY_CYC, t2 - t1);
+    atomicMax(prof + SR_SEL_MAX_CYC, t2 - t0);
+    atomicMax(prof + SR_SEL_MAX_SORT, t1 - t0);
+    atomicMax(prof + SR_SEL_MAX_GREEDY, t2 - t1);
   }
   // the ring's pick lists, sectors in order (the reference appends them sector by sector)
   if (wid == 0) {
@@ -864,28 +872,22 @@ __device__ inline void sr_ringvox(const SrDev& D, int r, int n, uint32_t* lds) {
   S.scratch_idx = reinterpret_cast<int*>(D.ss_b + base);
   S.scratch_cap = (uint32_t)n;
   S.err = &F.err;
-  S.hot.rk = D.ss_a + base;
-  S.hot.hl = reinterpret_cast<uint32_t*>(D.ss_e + base);
-  S.hot.hv = S.hot.hl + n;  // 3 words per hot voxel, at most n / 3 of them: within the ring's 2 n
-  S.hot.fpos = reinterpret_cast<uint32_t*>(D.ss_s + base);
-  S.hot.cap_h = (uint32_t)n / 3;
+  uint32_t* hl = reinterpret_cast<uint32_t*>(D.ss_e + base);  // then hv: 3 words per hot voxel, at most n / 3
+  S.hot = VxHot{D.ss_a + base, hl, hl + n, reinterpret_cast<uint32_t*>(D.ss_s + base), (uint32_t)n / 3};
   unsigned long long* prof = D.pdbg;
-  const unsigned long long t0 = __builtin_readcyclecounter();
-  voxel_segment(S, lds);
-  const unsigned long long t1 = __builtin_readcyclecounter();
-  const int heap_el = vh_fixup<SRV_THREADS>(VxSrc{S.src0, n, nullptr}, n, S.out, S.hot, lds, VX_LDS_WORDS - 256,
-                                            *reinterpret_cast<VxMisc*>(lds + VX_LDS_WORDS - 192), nullptr, &F.err,
-                                            prof, prof ? prof + 8 : nullptr);
+  unsigned long long t0 = __builtin_readcyclecounter(), t1;
+  const VhDiag C{prof ? prof + SR_VOX_HOT : nullptr, prof ? prof + SR_VOX_SORT : nullptr, nullptr, &t1};
+  const int heap_el = vx_filter_exact<SRV_THREADS>(S, VxSrc{S.src0, n, nullptr}, n, lds, nullptr, &F.err, C);
   if (prof && threadIdx.x == 0) {  // (diagnostics: include/loam_core.h LOAM_SR_DEBUG_COUNTERS)
     const unsigned long long t2 = __builtin_readcyclecounter();
-    atomicAdd(prof + 4, t1 - t0);
-    atomicAdd(prof + 5, (unsigned long long)n);
-    atomicMax(prof + 6, (unsigned long long)n);
-    atomicMax(prof + 7, (unsigned long long)heap_el);
+    atomicAdd(prof + SR_VOX_SEG_CYC, t1 - t0);
+    atomicAdd(prof + SR_VOX_PTS, (unsigned long long)n);
+    atomicMax(prof + SR_VOX_MAX_PTS, (unsigned long long)n);
+    atomicMax(prof + SR_VOX_MAX_HEAP, (unsigned long long)heap_el);
     // the slowest ring: its cycles in the high bits, then its heap-sorted elements and points
-    atomicMax(prof + 3, t2 - t0);
-    atomicMax(prof + 16, ((t2 - t0) << 32) | ((unsigned long long)heap_el << 16) | (unsigned long long)n);
-    atomicMax(prof + 18, ((t2 - t0) << 32) | (t2 - t1));
+    atomicMax(prof + SR_VOX_MAX_CYC, t2 - t0);
+    atomicMax(prof + SR_VOX_SLOWEST, ((t2 - t0) << 32) | ((unsigned long long)heap_el << 16) | (unsigned long long)n);
+    atomicMax(prof + SR_VOX_SLOWEST_FIX, ((t2 - t0) << 32) | (t2 - t1));
   }
 }
 

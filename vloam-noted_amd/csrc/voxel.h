@@ -148,7 +148,20 @@ struct VxMisc {
   VxGeom g;
   float bb[VX_WAVES][6];
 };
-static_assert(sizeof(VxMisc) <= 192 * 4, "misc area");
+// The tail of a filter's LDS (LW words): scan scratch, then VxMisc at the last VX_MISC_WORDS, whose
+// last VX_PARK_WORDS are the caller's own (revox_item: vx_park_block, vx_park_result)
+constexpr int VX_TAIL_WORDS = 256, VX_MISC_WORDS = 192, VX_PARK_WORDS = 3;
+static_assert(sizeof(VxMisc) <= (VX_MISC_WORDS - VX_PARK_WORDS) * 4, "misc area");
+template <int LW = VX_LDS_WORDS>
+__device__ inline uint32_t* vx_ws(uint32_t* lds) { return lds + LW - VX_TAIL_WORDS; }
+template <int LW = VX_LDS_WORDS>
+__device__ inline VxMisc& vx_misc(uint32_t* lds) { return *reinterpret_cast<VxMisc*>(lds + LW - VX_MISC_WORDS); }
+// (of a VX_LDS_WORDS filter) one word: its block of the sort scratch; two: the cube's new offset and count
+__device__ inline uint32_t* vx_park_block(uint32_t* lds) { return lds + VX_LDS_WORDS - VX_PARK_WORDS; }
+__device__ inline uint32_t* vx_park_result(uint32_t* lds) { return lds + VX_LDS_WORDS - (VX_PARK_WORDS - 1); }
+// relative slots of VoxSeg::prof_seg (the full filter; VXS_DETAIL: vx_centroids' two) and ::prof (the merge)
+enum { VXS_BBOX = 0, VXS_HASH = 1, VXS_SORT = 2, VXS_MEMBERS = 3, VXS_DETAIL = 4, VXS_SLOTS = 6 };
+enum { VXM_BBOX = 0, VXM_PASS_A = 1, VXM_SORT = 2, VXM_PASS_B = 3, VXM_SLOTS = 4 };
 
 
 // a hot voxel (output slot, cnt members member(0 ..)) -> hv / hl / rk.  One thread; counters in M
@@ -181,7 +194,7 @@ constexpr uint32_t VX_OVERFLOW = 0xFFFFFFFFu;  // vx_group: unique voxels exceed
 constexpr int VX_NB = 2048;                    // idx buckets of the grouped path
 constexpr int VX_HIST_WORD = 3 * VX_UCAP;      // LDS words [36864, 38912): bucket histogram
 constexpr int VX_GEND_WORD = VX_HIST_WORD + VX_NB;  // [38912, 40704): group ends
-constexpr int VX_MAX_GROUPS = VX_LDS_WORDS - 256 - VX_GEND_WORD;
+constexpr int VX_MAX_GROUPS = VX_LDS_WORDS - VX_TAIL_WORDS - VX_GEND_WORD;
 
 constexpr int VX_UNROLL = 4;
 
@@ -383,7 +396,7 @@ __device__ inline uint32_t vx_group(const VoxSeg& S, const VxGeom& g, const VxSr
   uint32_t mpos = vx_block_scan(nm, ws, &U);
   const int fail = M.sfail;
   __syncthreads();
-  vx_phase(S.prof_seg, 1, &tp);
+  vx_phase(S.prof_seg, VXS_HASH, &tp);
   if (U > VX_UCAP || fail) return VX_OVERFLOW;
   uint32_t Upad = 64;
   while (Upad < U) Upad <<= 1;
@@ -439,7 +452,7 @@ __device__ inline uint32_t vx_group(const VoxSeg& S, const VxGeom& g, const VxSr
   uint32_t* ukey = lds;  // packed: ukey[U] | uoff[U] | ufill[U] | LDS member lists
   uint32_t* uoff = lds + U;
   uint32_t* ufill = lds + 2 * U;
-  vx_phase(S.prof_seg, 2, &tp);
+  vx_phase(S.prof_seg, VXS_SORT, &tp);
 #pragma unroll
   for (int e = 0; e < EPT; ++e) {
     uint32_t j = tid * EPT + e;
@@ -472,7 +485,7 @@ __device__ inline uint32_t vx_group(const VoxSeg& S, const VxGeom& g, const VxSr
   if (N <= 65536u && 3 * U + mem_words + 64 <= lds_limit) {
     uint32_t* big = lds + 3 * U + mem_words;
     moved = vx_centroids(g, P, N, reinterpret_cast<uint16_t*>(lds + 3 * U), klo, khi, U, ukey, uoff,
-                         ufill, S.out + ob, big, lds_limit - (3 * U + mem_words), M, S.prof_seg ? S.prof_seg + 4 : nullptr,
+                         ufill, S.out + ob, big, lds_limit - (3 * U + mem_words), M, S.prof_seg ? S.prof_seg + VXS_DETAIL : nullptr,
                          S.hot.rk ? &S.hot : nullptr, rank0);
   } else {
     uint32_t* big = lds + 3 * U;
@@ -482,7 +495,7 @@ __device__ inline uint32_t vx_group(const VoxSeg& S, const VxGeom& g, const VxSr
   }
   if (moved) M.moved = 1;
   __syncthreads();
-  vx_phase(S.prof_seg, 3, &tp);
+  vx_phase(S.prof_seg, VXS_MEMBERS, &tp);
   *moved_out |= M.moved;
   if (out_base == VX_ALLOC && tid == 0) {
     if (S.res_off) *S.res_off = ob;
@@ -629,8 +642,8 @@ __device__ inline void vx_geometry(const PF& P, uint32_t N, float leaf, VxMisc& 
 __device__ inline void voxel_segment(const VoxSeg& S, uint32_t* lds) {
   const int tid = threadIdx.x;
   const int wid = tid >> 6, lane = tid & 63;
-  uint32_t* ws = lds + VX_LDS_WORDS - 256;  // scan scratch (64 words)
-  VxMisc& M = *reinterpret_cast<VxMisc*>(lds + VX_LDS_WORDS - 192);
+  uint32_t* ws = vx_ws(lds);  // scan scratch (64 words)
+  VxMisc& M = vx_misc(lds);
   if (tid == 0) {
     M.hot_n = 0;
     M.hot_l = 0;
@@ -724,7 +737,7 @@ __device__ inline void voxel_segment(const VoxSeg& S, uint32_t* lds) {
   unsigned long long tp = __builtin_readcyclecounter();
   vx_geometry(P, N, S.leaf, M);
   const VxGeom g = M.g;
-  vx_phase(S.prof_seg, 0, &tp);
+  vx_phase(S.prof_seg, VXS_BBOX, &tp);
   if (g.overflow) {  // PCL: "Leaf size is too small" -> output = input
     if (tid == 0) {
       uint32_t b = S.tail ? atomicAdd(S.tail, N) : 0;
@@ -749,7 +762,7 @@ __device__ inline void voxel_segment(const VoxSeg& S, uint32_t* lds) {
   // ---- 3-6 in one LDS pass when the unique voxels fit, else in idx-range groups
   const VxSrc src{S.src0, n0, sec};
   int moved = 0;
-  uint32_t U = vx_group(S, g, src, N, members, 0u, 0xFFFFFFFFu, VX_ALLOC, VX_LDS_WORDS - 256, lds, ws,
+  uint32_t U = vx_group(S, g, src, N, members, 0u, 0xFFFFFFFFu, VX_ALLOC, VX_LDS_WORDS - VX_TAIL_WORDS, lds, ws,
                         M, &moved);
   if (U != VX_OVERFLOW) return;
   vx_grouped(S, g, src, N, members, lds, ws, M);
@@ -873,7 +886,7 @@ template <int NT = VX_THREADS, int CAP = (int)VX_MERGE_CAP, int LW = VX_LDS_WORD
 __device__ inline bool vx_merge_fixed_point(const VoxSeg& S, uint32_t* lds) {
   constexpr int TMAX = 2 * CAP;       // hash slots (load factor <= 1/2)
   constexpr int RX = 2 * TMAX + CAP;  // start of the shared region: C hits, then the sort
-  static_assert(RX + 4 * CAP <= LW - 256, "merge LDS layout");
+  static_assert(RX + 4 * CAP <= LW - VX_TAIL_WORDS, "merge LDS layout");
   static_assert(CAP <= 4 * NT && (CAP & (CAP - 1)) == 0, "merge: at most 4 new points per thread");
   constexpr int U = VX_UNROLL;       // C points per thread kept in registers
   constexpr int UA = CAP / NT;       // A points per thread
@@ -881,8 +894,8 @@ __device__ inline bool vx_merge_fixed_point(const VoxSeg& S, uint32_t* lds) {
   static_assert(SPT <= 32, "new-only flags in one word");
   constexpr uint32_t NONE = 0xFFFFFFFFu;
   const int tid = threadIdx.x;
-  uint32_t* ws = lds + LW - 256;
-  VxMisc& M = *reinterpret_cast<VxMisc*>(lds + LW - 192);
+  uint32_t* ws = vx_ws<LW>(lds);
+  VxMisc& M = vx_misc<LW>(lds);
   const float4* C = S.src0;
   const float4* A = S.src1;
   const uint32_t n0 = (uint32_t)S.n0, n1 = (uint32_t)S.n1;
@@ -935,7 +948,7 @@ __device__ inline bool vx_merge_fixed_point(const VoxSeg& S, uint32_t* lds) {
     vx_geometry_finish<NT>(mnx, mny, mnz, mxx, mxy, mxz, S.leaf, M);
     g = M.g;
   }
-  vx_phase(S.prof, 0, &tp);
+  vx_phase(S.prof, VXM_BBOX, &tp);
   if (g.overflow) return false;
   // anchored keys are valid only inside the key box: checked for every point on the way (pass A)
   int bad = 0;
@@ -1032,7 +1045,7 @@ __device__ inline bool vx_merge_fixed_point(const VoxSeg& S, uint32_t* lds) {
   if (bad) atomicOr(&M.sfail, 1);
   __syncthreads();
   if (W && __builtin_amdgcn_readfirstlane(M.sfail)) return false;  // a point outside the anchored key box: full filter
-  vx_phase(S.prof, 1, &tp);
+  vx_phase(S.prof, VXM_PASS_A, &tp);
   // 4. the voxels holding A points only, listed then sorted by key
   uint32_t fmask = 0, cnt = 0;
 #pragma unroll
@@ -1067,7 +1080,7 @@ __device__ inline bool vx_merge_fixed_point(const VoxSeg& S, uint32_t* lds) {
   // bdir[b] the first voxel of a bucket >= b (bdir[MB] = Dn), so a lookup searches one bucket
   // (~Dn / MB voxels) instead of all Dn (pass B looks up every C point)
   constexpr int MB = 1024;
-  static_assert(RX + 4 * CAP + MB + 1 <= LW - 256, "merge LDS layout: bucket directory");
+  static_assert(RX + 4 * CAP + MB + 1 <= LW - VX_TAIL_WORDS, "merge LDS layout: bucket directory");
   uint32_t* bdir = lds + RX + 4 * CAP;
   const uint32_t kmin = Dn ? (uint32_t)(srt[0] >> 32) : 0u, kmax = Dn ? (uint32_t)(srt[Dn - 1] >> 32) : 0u;
   int sh = 0;
@@ -1091,7 +1104,7 @@ __device__ inline bool vx_merge_fixed_point(const VoxSeg& S, uint32_t* lds) {
     M.sbase[1] = b;
   }
   __syncthreads();
-  vx_phase(S.prof, 2, &tp);
+  vx_phase(S.prof, VXM_SORT, &tp);
   const uint32_t ob = M.sbase[1];
   if (ob == 0xFFFFFFFFu) return true;
   float4* out = S.out + ob;
@@ -1217,7 +1230,7 @@ __device__ inline bool vx_merge_fixed_point(const VoxSeg& S, uint32_t* lds) {
   }
   if (moved) M.moved = 1;
   __syncthreads();
-  vx_phase(S.prof, 3, &tp);
+  vx_phase(S.prof, VXM_PASS_B, &tp);
   if (tid == 0) {
     if (S.res_off) *S.res_off = ob;
     if (S.res_cnt) *S.res_cnt = n0 + Dn;

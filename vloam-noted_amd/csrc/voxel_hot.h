@@ -75,6 +75,11 @@ static inline void vh_spin_limit_from_env(int device) {
   if (hipMemcpyToSymbol(HIP_SYMBOL(vh_spin_limit_g), &v, sizeof(v)) == hipSuccess) done |= 1ull << device;
 }
 
+// relative slots of the diagnostics counters: vh_sort's prof, its detail dprof (VhCtl), vh_fixup's prof
+enum { VHS_HEAP_EL, VHS_SETUP, VHS_LEVELS, VHS_SUBTREES, VHS_POS, VHS_SLOTS };
+enum { VHD_PART, VHD_BUSY = 5, VHD_LONGEST, VHD_HEAP_CYC, VHD_SUBTREES, VHD_SLOTS };
+enum { VHF_SORT, VHF_CENTROIDS, VHF_FILTERS, VHF_SLOTS };
+
 struct VhLess {
   __device__ bool operator()(uint32_t a, uint32_t b) const { return (a >> 16) < (b >> 16); }
 };
@@ -129,7 +134,7 @@ template <int NT>
 constexpr int vh_lds_words(int n) {
   return n + n / 4 + 2 + VH_ROOTS + 2 * VH_BIGC + (NT / 64) * VH_WAVE_W + (int)(sizeof(VhCtl) / 4) + 1;
 }
-static_assert(vh_lds_words<VX_THREADS>(VH_MAX_N) <= VX_LDS_WORDS - 256, "hot sort LDS layout");
+static_assert(vh_lds_words<VX_THREADS>(VH_MAX_N) <= VX_LDS_WORDS - VX_TAIL_WORDS, "hot sort LDS layout");
 
 // One segment [lo, hi) (65 < m <= 64 U + 1) partitioned by one wave: lane l classifies the c
 // consecutive positions lo + 1 + l c .. (c = ceil((m - 1) / 64) <= U) into two bit masks, one
@@ -252,7 +257,7 @@ __device__ inline int vh_partition_wave_u(uint32_t* E, uint16_t* Bs, int lo, int
 __device__ inline int vh_partition_wave(uint32_t* E, uint16_t* Bs, int lo, int hi, unsigned long long* dp = nullptr) {
   static_assert(VH_BIG == 1024, "size classes");
   const int m = hi - lo;  // positions lo + 1 .. hi - 1: m - 1 of them
-  if (dp && (threadIdx.x & 63) == 0) atomicAdd(dp + (m <= 65 ? 0 : m <= 129 ? 1 : m <= 257 ? 2 : m <= 513 ? 3 : 4), 1ull);
+  if (dp && (threadIdx.x & 63) == 0) atomicAdd(dp + VHD_PART + (m <= 65 ? 0 : m <= 129 ? 1 : m <= 257 ? 2 : m <= 513 ? 3 : 4), 1ull);
   if (m <= 129) return vh_partition_wave_u<2>(E, Bs, lo, hi);
   if (m <= 257) return vh_partition_wave_u<4>(E, Bs, lo, hi);
   if (m <= 513) return vh_partition_wave_u<8>(E, Bs, lo, hi);
@@ -624,7 +629,7 @@ __device__ inline void vh_wave_subtree(uint32_t* E, uint16_t* Bs, uint32_t root,
       if (d == 0) {
         const unsigned long long th = __builtin_readcyclecounter();
         vh_depth_limit_wave(E, lo, hi, kb, heap_el);
-        if (dp && lane == 0) atomicAdd(dp + 7, __builtin_readcyclecounter() - th);
+        if (dp && lane == 0) atomicAdd(dp + VHD_HEAP_CYC, __builtin_readcyclecounter() - th);
       } else {
         const int cut = vh_partition_wave(E, Bs, lo, hi, dp);
         if (cut >= 0) {
@@ -718,12 +723,12 @@ __device__ inline void vh_drain(const VhLds& L) {
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");  // its listings before its end
       atomicSub(&C->pending, 1);
     }
-    if (dp && lane == 0) atomicAdd(dp + 8, 1ull);
+    if (dp && lane == 0) atomicAdd(dp + VHD_SUBTREES, 1ull);
   }
   if (dp && lane == 0) {
     const unsigned long long b = __builtin_readcyclecounter() - t0;
-    atomicAdd(dp + 5, b);
-    atomicMax(dp + 6, b);
+    atomicAdd(dp + VHD_BUSY, b);
+    atomicMax(dp + VHD_LONGEST, b);
   }
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -1012,7 +1017,7 @@ __device__ inline int vh_sort(uint32_t* lds, int n, const VxHot& H, int* err, un
     }
   }
   __syncthreads();
-  vx_phase(prof ? prof + 1 : nullptr, 0, &tp);
+  vx_phase(prof ? prof + VHS_SETUP : nullptr, 0, &tp);
   for (int lev = 0;; ++lev) {
     const int cur = lev & 1, nxt = cur ^ 1;
     const int nb = min(C->nbig[cur], VH_BIGC);
@@ -1059,15 +1064,15 @@ __device__ inline int vh_sort(uint32_t* lds, int n, const VxHot& H, int* err, un
   }
   if (prof && tid == 0) {  // the workgroup levels without the drains inside them
     const unsigned long long now = __builtin_readcyclecounter();
-    atomicAdd(prof + 2, now - tp - t_drain);
-    atomicAdd(prof + 3, t_drain);
+    atomicAdd(prof + VHS_LEVELS, now - tp - t_drain);
+    atomicAdd(prof + VHS_SUBTREES, t_drain);
     tp = now;
   }
   vh_drain<NT>(L);
-  vx_phase(prof ? prof + 3 : nullptr, 0, &tp);
+  vx_phase(prof ? prof + VHS_SUBTREES : nullptr, 0, &tp);
   if (tid == 0 && C->err) atomicOr(err, C->err);
   const int heap_el = C->heap_el;
-  if (tid == 0 && prof) atomicAdd(prof, (unsigned long long)heap_el);
+  if (tid == 0 && prof) atomicAdd(prof + VHS_HEAP_EL, (unsigned long long)heap_el);
   for (int q = tid; q < n; q += NT) {
     const uint32_t e = L.E[q];
     if (e & VH_HOT) {
@@ -1076,7 +1081,7 @@ __device__ inline int vh_sort(uint32_t* lds, int n, const VxHot& H, int* err, un
     }
   }
   __syncthreads();
-  vx_phase(prof ? prof + 4 : nullptr, 0, &tp);
+  vx_phase(prof ? prof + VHS_POS : nullptr, 0, &tp);
   return heap_el;
 }
 
@@ -1328,12 +1333,33 @@ __device__ __attribute__((always_inline)) inline int vh_fixup(const PF& P, int n
   const bool mv = vh_centroids<NT>(P, o, H, g, lds, lds_words, M, err);
   if (mv && threadIdx.x == 0 && stable_out) *stable_out = 0u;
   if (prof && threadIdx.x == 0) {
-    atomicAdd(prof, t1 - t0);
-    atomicAdd(prof + 1, __builtin_readcyclecounter() - t1);
-    atomicAdd(prof + 2, 1ull);
+    atomicAdd(prof + VHF_SORT, t1 - t0);
+    atomicAdd(prof + VHF_CENTROIDS, __builtin_readcyclecounter() - t1);
+    atomicAdd(prof + VHF_FILTERS, 1ull);
   }
   __syncthreads();
   return heap_el;
+}
+
+// The exact-order filter of S (S.hot set) on its n <= VH_BIG_N points P(0 .. n), the one copy of the
+// chain: the input-order pass (the merge when the caller says the cube qualifies, `fixed`; *merged: it
+// ran), then vh_fixup (tok, err: its own), whose result it returns.
+// VhDiag (optional diagnostics): vh_fixup's three counter bases, the cycle counter between the passes
+struct VhDiag { unsigned long long *prof = nullptr, *sprof = nullptr, *dprof = nullptr, *t_mid = nullptr; };
+template <int NT, typename PF>
+__device__ __attribute__((always_inline)) inline int vx_filter_exact(
+    const VoxSeg& S, const PF& P, int n, uint32_t* lds, uint32_t* tok, int* err, const VhDiag& C = {}, bool fixed = false,
+    bool* merged = nullptr) {
+  bool mg = false;
+  if (fixed) {
+    mg = vx_merge_fixed_point<NT, (int)VX_MERGE_CAP, VX_LDS_WORDS, true>(S, lds);
+    __syncthreads();  // false: grid overflow, full filter below
+  }
+  if (!mg) voxel_segment(S, lds);
+  if (merged) *merged = mg;
+  if (C.t_mid) *C.t_mid = __builtin_readcyclecounter();
+  return vh_fixup<NT>(P, n, S.out, S.hot, lds, VX_LDS_WORDS - VX_TAIL_WORDS, vx_misc(lds), tok, err, C.prof,
+                      C.sprof, C.dprof);
 }
 
 }  // namespace loam

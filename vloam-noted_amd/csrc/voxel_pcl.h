@@ -32,6 +32,8 @@ struct VxPclDefer {
   SsLevels* LL;  // LDS
 };
 
+// relative slots of VxPclScratch::prof (a sort in global memory: VXP_SORT its deferred segments, its own levels in glob)
+enum { VXP_KEYS = 0, VXP_SORT = 1, VXP_FINAL = 2, VXP_CENTROIDS = 3 };
 struct VxPclScratch {
   uint64_t* E;   // n: (idx << 32 | point), permuted by the sort
   uint32_t* A;   // n
@@ -124,7 +126,7 @@ __device__ inline void voxel_grid_pcl(const PF& P, int n, float leaf, const VxPc
   }
   const VxIdxLess less;
   __syncthreads();
-  vx_phase(X.prof, 0, &tp);
+  vx_phase(X.prof, VXP_KEYS, &tp);
   if constexpr (DEFER) {
     ss_levels<true, NT, true>(X.E, X.A, X.B, X.lev, tid >> 6, NT / 64, less, X.seg[0], X.seg[1], X.loc, dfr->dseg);
     __syncthreads();
@@ -135,11 +137,11 @@ __device__ inline void voxel_grid_pcl(const PF& P, int n, float leaf, const VxPc
     ss_levels<true, NT>(X.E, X.A, X.B, X.lev, tid >> 6, NT / 64, less, X.seg[0], X.seg[1], X.loc);
   }
   __syncthreads();
-  vx_phase(X.prof, 1, &tp);
+  vx_phase(X.prof, VXP_SORT, &tp);
   if (tid == 0 && X.lev->err) atomicOr(err, 4);
   ss_final(X.E, X.A, X.B, n, X.S, tid, NT, less);
   __syncthreads();
-  vx_phase(X.prof, 2, &tp);
+  vx_phase(X.prof, VXP_FINAL, &tp);
   // runs of equal idx: thread t owns positions [t * per, (t + 1) * per)
   const int per = (n + NT - 1) / NT;
   const int p0 = min(n, tid * per), p1 = min(n, p0 + per);
@@ -172,7 +174,7 @@ __device__ inline void voxel_grid_pcl(const PF& P, int n, float leaf, const VxPc
   }
   if (moved) M.moved = 1;
   __syncthreads();
-  vx_phase(X.prof, 3, &tp);
+  vx_phase(X.prof, VXP_CENTROIDS, &tp);
   if (tid == 0) finish(b, tot, M.moved == 0);
 }
 
