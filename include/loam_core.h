@@ -495,6 +495,66 @@ int32_t loam_vo_solve(int32_t device, int32_t n_problems, const int32_t* offsets
                       double* x, int32_t max_iterations, loam_lm_stats* st);
 
 /* --------------------------------------------------------------------------------------
+ * The VO frame on the device — everything of VisualOdometry::solveNlsAll between the ORB
+ * descriptors and angles_0to1 / t_0to1 (visual_odometry.cpp:304-509), n_pairs independent frame
+ * pairs per handle and call: ImageUtil::matchDescriptors (image_util.cpp:347-438: BFMatcher
+ * NORM_HAMMING, knnMatch k = 2, ratio test), the outlier gate (:363-368), queryDepth of the
+ * previous point (:371), the CostFunctor32 / CostFunctor22 records (:400-474) and the solve, as
+ * one launch sequence.  Keypoint detection and ORB description stay with OpenCV.
+ * ------------------------------------------------------------------------------------ */
+typedef struct loam_vo_frames loam_vo_frames;
+typedef struct loam_vo_frames_params {
+  float   P_rect0[12];        /* 3x4 row-major; only leftCols(3) is used (visual_odometry.cpp:409) */
+  int32_t remove_vo_outlier;  /* 100 (vloam_main.launch:6); <= 0 disables the gate (:363-368) */
+  double  match_ratio;        /* 0.8 (image_util.cpp:417); in (0, 1] */
+  int32_t desc_bytes;         /* 32 (ORB); any multiple of 4 in 4..64 */
+  int32_t depth_radius;       /* 2 (queryDepth's searching_radius) */
+  int32_t max_iterations;     /* 100 (visual_odometry.cpp:70) */
+  int32_t max_keypoints;      /* per image, default 8192 */
+} loam_vo_frames_params;
+/* the values above; P_rect0 zero (set it from the calibration) */
+void    loam_vo_frames_params_default(loam_vo_frames_params* p);
+/* bound to a loam_depth handle (same device; it must outlive this handle) */
+int32_t loam_vo_frames_create(const loam_vo_frames_params* p, loam_depth* depth, int32_t n_pairs,
+                              loam_vo_frames** out);
+int32_t loam_vo_frames_destroy(loam_vo_frames* h);
+/* descriptors of the previous (0) and current (1) image (n x desc_bytes, row-major) + keypoint
+ * pixel coordinates (2 floats each); host memory, copied.  depth_stream_prev = the loam_depth
+ * stream holding the previous frame's buckets (point_cloud_utils[1 - i]); they are read by
+ * loam_vo_frames_solve.  An input replaces the pair's earlier one and is consumed by the solve. */
+int32_t loam_vo_frames_input_descriptors(loam_vo_frames* h, int32_t pair, const float* kp0_xy,
+                                         const uint8_t* desc0, int32_t n0, const float* kp1_xy,
+                                         const uint8_t* desc1, int32_t n1, int32_t depth_stream_prev);
+/* optical_flow_match = true (:349-360): already paired points + LK status (kept where == 1);
+ * no matching */
+int32_t loam_vo_frames_input_tracks(loam_vo_frames* h, int32_t pair, const float* prev_xy, const float* curr_xy,
+                                    const uint8_t* status, int32_t n, int32_t depth_stream_prev);
+/* initial angles_0to1, t_0to1 of the pair's solves from now on (:311-331); NULL = zeros
+ * (reset_VO_to_identity, the default) */
+int32_t loam_vo_frames_set_initial(loam_vo_frames* h, int32_t pair, const double* x6);
+/* every pair with an input: match -> gate -> queryDepth -> records -> solve, no host round trip
+ * between the steps */
+int32_t loam_vo_frames_solve(loam_vo_frames* h);
+typedef struct loam_vo_frame_stats {
+  int32_t n_knn;      /* knn_matches.size(): query descriptors with two neighbours (tracks: n) */
+  int32_t n_matches;  /* after the ratio test (tracks: status == 1) */
+  int32_t n_gated;    /* after the outlier gate = residual blocks */
+  int32_t counter32, counter22;
+  double ms;          /* device time of the whole call (all pairs) */
+} loam_vo_frame_stats;
+/* results of the last solve that had an input for the pair (each pointer may be NULL).  A pair
+ * with no surviving record: LOAM_OK, termination = 4, x6 = its initial values */
+int32_t loam_vo_frames_result(loam_vo_frames* h, int32_t pair, double* x6, loam_lm_stats* lm,
+                              loam_vo_frame_stats* st);
+/* for parity tests and the node's match visualisation: (queryIdx, trainIdx, distance) int32
+ * triples in query order (tracks: (j, j, 0)); the surviving records (10 doubles each,
+ * loam_vo_solve's layout) and their depth0 (each may be NULL); copy when cap >= count; return
+ * count */
+int32_t loam_vo_frames_matches_copy(loam_vo_frames* h, int32_t pair, int32_t* out, int32_t cap);
+int32_t loam_vo_frames_records_copy(loam_vo_frames* h, int32_t pair, double* records, float* depth0,
+                                    int32_t cap);
+
+/* --------------------------------------------------------------------------------------
  * Device LM engine on an explicit factor list (lidarFactor.hpp + Ceres TR-LM).  Factor
  * record = 10 doubles: type (1 LidarEdgeFactor, 2 LidarPlaneFactor, 3 LidarPlaneNormFactor),
  * curr_point[3], a[3], b[3] (edge: last_point_a/b; plane: j, unit normal ljm; plane-norm:

@@ -3,6 +3,8 @@
 //   vloam::ScanRegistration  scan_registration.h:64-81   -> loam_amd::ScanRegistration
 //   vloam::LaserOdometry     laser_odometry.h:70-84      -> loam_amd::LaserOdometry
 //   vloam::LaserMapping      laser_mapping.h:85-100      -> loam_amd::LaserMapping
+//   vloam::VisualOdometry::solveNlsAll + ImageUtil::matchDescriptors
+//                                                        -> loam_amd::VisualOdometryFrames
 // Clouds cross the boundary as packed float4 (x, y, z, intensity) arrays. pcl::PointXYZI
 // is 32 bytes, so the node packs and unpacks it (INTEGRATION.md shows the adapter). Errors
 // throw loam_amd::Error carrying the LOAM_ERR_* code and loam_last_error(). There is no
@@ -234,6 +236,63 @@ class LaserMapping {
 
  private:
   BatchMapper m_;
+};
+
+inline loam_vo_frames_params default_vo_frames_params() {
+  loam_vo_frames_params p;
+  loam_vo_frames_params_default(&p);
+  return p;
+}
+
+// VisualOdometry::solveNlsAll with the matcher in front of it (visual_odometry.cpp:304-509,
+// image_util.cpp:347-438), n_pairs frame pairs per call: descriptors or LK tracks in,
+// angles_0to1 / t_0to1 out.  `depth` is the loam_depth handle whose streams hold the previous
+// frames' buckets (point_cloud_utils[1 - i]); it must outlive this object.
+class VisualOdometryFrames {
+ public:
+  struct Match {  // cv::DMatch's fields
+    int32_t queryIdx, trainIdx, distance;
+  };
+
+  VisualOdometryFrames(const loam_vo_frames_params& p, loam_depth* depth, int32_t n_pairs = 1) {
+    check(loam_vo_frames_create(&p, depth, n_pairs, &h_));
+  }
+  ~VisualOdometryFrames() { loam_vo_frames_destroy(h_); }
+  VisualOdometryFrames(const VisualOdometryFrames&) = delete;
+  VisualOdometryFrames& operator=(const VisualOdometryFrames&) = delete;
+
+  // keypoints[1 - i] / descriptors[1 - i] (0) and keypoints[i] / descriptors[i] (1): pixel
+  // coordinates (2 floats each) and descriptor rows of params.desc_bytes
+  void inputDescriptors(int32_t pair, const float* kp0_xy, const uint8_t* desc0, int32_t n0, const float* kp1_xy,
+                        const uint8_t* desc1, int32_t n1, int32_t depth_stream_prev) {
+    check(loam_vo_frames_input_descriptors(h_, pair, kp0_xy, desc0, n0, kp1_xy, desc1, n1, depth_stream_prev));
+  }
+  // optical_flow_match: keypoints_2f[1 - i], keypoints_2f[i], optical_flow_status
+  void inputTracks(int32_t pair, const float* prev_xy, const float* curr_xy, const uint8_t* status, int32_t n,
+                   int32_t depth_stream_prev) {
+    check(loam_vo_frames_input_tracks(h_, pair, prev_xy, curr_xy, status, n, depth_stream_prev));
+  }
+  // angles_0to1 ++ t_0to1 the solves start from; nullptr: zeros (reset_VO_to_identity)
+  void setInitial(int32_t pair, const double* x6 = nullptr) { check(loam_vo_frames_set_initial(h_, pair, x6)); }
+  void solveNlsAll() { check(loam_vo_frames_solve(h_)); }
+  // x6 = angles_0to1 ++ t_0to1; returns the Ceres summary's counts
+  loam_lm_stats result(int32_t pair, double x6[6], loam_vo_frame_stats* st = nullptr) const {
+    loam_lm_stats lm;
+    check(loam_vo_frames_result(h_, pair, x6, &lm, st));
+    return lm;
+  }
+  // the accepted matches in query order (for cv::drawMatches)
+  std::vector<Match> matches(int32_t pair) const {
+    static_assert(sizeof(Match) == 3 * sizeof(int32_t), "Match is three packed int32");
+    const int32_t n = check(loam_vo_frames_matches_copy(h_, pair, nullptr, 0));
+    std::vector<Match> out(static_cast<size_t>(n));
+    if (n) check(loam_vo_frames_matches_copy(h_, pair, &out[0].queryIdx, n));
+    return out;
+  }
+  loam_vo_frames* handle() const { return h_; }
+
+ private:
+  loam_vo_frames* h_ = nullptr;
 };
 
 }  // namespace loam_amd

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "common.h"
+#include "depth_dev.h"
 
 namespace loam {
 
@@ -33,33 +34,6 @@ constexpr int DP_THREADS = 256;
 constexpr int DP_CHUNK = 4 * DP_THREADS;  // points per projection workgroup (contiguous)
 constexpr int DP_SCAN_THREADS = 1024;
 constexpr int DP_ERR_CAP = 1;
-
-struct DepthFrame {
-  const float* xyz;  // input points (stride floats each)
-  int n, stride;
-  int active;
-  int n_front, n_dnsp;
-  int err;
-};
-
-struct DepthDev {
-  int B, cap, W, H, nchunk;  // nchunk: chunks per stream (cap / DP_CHUNK)
-  float grid;
-  float A[16], Bm[16], C[12];  // cam_T_velo, rect0_T_cam, P_rect0 (row-major)
-  DepthFrame* fr;
-  float4* tmp;       // [B][cap] (u, v, depth, bucket as float bits or -1)
-  int* chunk_cnt;    // [B][nchunk] front points per chunk -> offsets
-  float4* p2d;       // [B][cap] point_cloud_2d (u, v, depth)
-  int* bcnt;         // [B][W*H] bucket_count
-  int* bstart;       // [B][W*H + 1] member list starts
-  int* bfill;        // [B][W*H]
-  int* bslot;        // [B][W*H] dnsp slot (occupied buckets)
-  int* members;      // [B][cap] front rank of each bucketed point, grouped by bucket
-  float* bx;         // [B][W*H]
-  float* by;
-  float* bd;
-  float4* dnsp;      // [B][W*H]
-};
 
 // r[j] = sum_k v[k] M[j][k] (row vector times M^T), k in order, no contraction
 __device__ inline void dp_mul_t(const float* v, const float* M, int rows, float* r) {
@@ -276,7 +250,7 @@ __global__ void __launch_bounds__(DP_THREADS) k_dp_bucket(DepthDev D, int blocks
   D.dnsp[(size_t)s * WH + slot] = make_float4(x, y, d, 0.f);
 }
 
-// queryDepth (point_cloud_util.cpp:381-487) of nq image points of stream s
+// queryDepth (dp_query_one, depth_dev.h) of nq image points, each in its own stream
 __global__ void __launch_bounds__(DP_THREADS) k_dp_query(DepthDev D, const int* q_stream, const float2* xy, int nq,
                                                          int radius, float* depth) {
   const int q = blockIdx.x * DP_THREADS + threadIdx.x;
@@ -286,49 +260,7 @@ __global__ void __launch_bounds__(DP_THREADS) k_dp_query(DepthDev D, const int* 
     depth[q] = -1.0f;
     return;
   }
-  const int WH = D.W * D.H;
-  const int* bc = D.bcnt + (size_t)s * WH;
-  const float *bx = D.bx + (size_t)s * WH, *by = D.by + (size_t)s * WH, *bd = D.bd + (size_t)s * WH;
-  const float x = xy[q].x, y = xy[q].y;
-  const int ix = static_cast<int>(x / D.grid), iy = static_cast<int>(y / D.grid);
-  // the 3 nearest in gather order (a stable sort's first three), and the count
-  float nd[3] = {INFINITY, INFINITY, INFINITY}, nz[3] = {0.f, 0.f, 0.f};
-  int cnt = 0;
-  for (int i = ix - radius; i <= ix + radius; ++i)
-    for (int j = iy - radius; j <= iy + radius; ++j) {
-      if (!(i >= 0 && i < D.W && j >= 0 && j < D.H)) continue;
-      const int b = i * D.H + j;
-      if (bc[b] <= 0) continue;
-      ++cnt;
-      // std::pow(float, int) promotes to double (:407)
-      const double dx = (double)(x - bx[b]), dy = (double)(y - by[b]);
-      const float dist = (float)sqrt(dx * dx + dy * dy);
-      const float z = bd[b];
-      if (dist < nd[2]) {
-        if (dist < nd[1]) {
-          nd[2] = nd[1];
-          nz[2] = nz[1];
-          if (dist < nd[0]) {
-            nd[1] = nd[0];
-            nz[1] = nz[0];
-            nd[0] = dist;
-            nz[0] = z;
-          } else {
-            nd[1] = dist;
-            nz[1] = z;
-          }
-        } else {
-          nd[2] = dist;
-          nz[2] = z;
-        }
-      }
-    }
-  if (cnt < 10) {
-    depth[q] = -1.0f;
-    return;
-  }
-  depth[q] = (nz[0] * nd[1] * nd[2] + nz[1] * nd[0] * nd[2] + nz[2] * nd[0] * nd[1]) /
-             (0.0001f + nd[1] * nd[2] + nd[0] * nd[2] + nd[0] * nd[1]);
+  depth[q] = dp_query_one(D, s, xy[q].x, xy[q].y, radius);
 }
 
 }  // namespace loam
@@ -341,6 +273,7 @@ struct loam_depth {
   loam_depth_params P{};
   DepthDev D{};
   std::vector<DepthFrame> hf;
+  std::vector<char> processed;  // per stream: buckets of a loam_depth_process are resident
   std::vector<void*> allocs;
   float4* stage = nullptr;  // [B][cap] host-input staging
   int* d_qs = nullptr;      // query stream ids / points / results (grown on demand)
@@ -401,6 +334,19 @@ int32_t dp_query_cap(loam_depth* h, int n) {
 }
 
 }  // namespace
+
+namespace loam {
+
+int32_t depth_device_view(loam_depth* h, DepthDev* D, int* device) {
+  if (!h || !D || !device) return LOAM_ERR_ARG;
+  *D = h->D;
+  *device = h->dev;
+  return LOAM_OK;
+}
+
+bool depth_stream_processed(loam_depth* h, int s) { return h && s >= 0 && s < h->B && h->processed[s] != 0; }
+
+}  // namespace loam
 
 extern "C" {
 
@@ -469,6 +415,7 @@ int32_t loam_depth_create(const loam_depth_params* p, int32_t device, int32_t n_
   DA(D.dnsp, B * WH);
 #undef DA
   h->hf.assign(B, DepthFrame{});
+  h->processed.assign(B, 0);
   if (hipStreamSynchronize(h->st) != hipSuccess) return fail(LOAM_ERR_HIP);
   *out = h;
   return LOAM_OK;
@@ -546,7 +493,10 @@ int32_t loam_depth_process(loam_depth* h) {
   LOAM_HIP(hipMemcpyAsync(h->hf.data(), D.fr, sizeof(DepthFrame) * B, hipMemcpyDeviceToHost, st));
   LOAM_HIP(hipStreamSynchronize(st));
   LOAM_HIP(hipEventElapsedTime(&h->ms, h->ev[0], h->ev[1]));
-  for (auto& F : h->hf) F.active = 0;
+  for (int s = 0; s < B; ++s) {
+    if (h->hf[s].active) h->processed[s] = 1;
+    h->hf[s].active = 0;
+  }
   return LOAM_OK;
 }
 

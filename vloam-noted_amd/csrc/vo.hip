@@ -15,18 +15,22 @@
 //   type 5 (CostFunctor22): r = X1 . (t x q), q = R(w) X0: dr/dt = (q x X1)^T,
 //                           dr/dw = (X1 x t)^T dq/dw
 // One workgroup per problem runs all passes (evaluation -> block reduction -> step on one
-// lane), so a batch of B problems is one launch with no host round trip.
+// lane), so a batch of B problems is one launch with no host round trip.  The launch reads
+// device-resident records and offsets (vo_solve_launch, vo_dev.h): loam_vo_solve uploads a
+// caller's records for it, loam_vo_frames_solve (vo_frames.hip) hands it what k_vo_assemble wrote.
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
 #include "common.h"
 #include "lm.h"
+#include "vo_dev.h"
 
 namespace loam {
 
 constexpr int VO_THREADS = 256;
 constexpr int VO_MAX_PASSES = 256;  // >= max_num_iterations + 1 (invalid steps need no pass)
+static_assert(VO_MAX_ITERATIONS == VO_MAX_PASSES - 1, "vo_dev.h's cap is the kernel's pass budget");
 
 struct VoRot {
   double w[3];         // the rotation as Ceres' value path: unit axis, cos, sin, or first order
@@ -153,14 +157,16 @@ __device__ inline void vo_accum(int type, const double* rec, const VoRot& V, con
   }
 }
 
-// one workgroup per problem: every pass of the solve
-__global__ void __launch_bounds__(VO_THREADS) k_vo_solve(const double* factors, const int* off, double* xs,
-                                                          int max_iter, LmState* states) {
+// one workgroup per problem: every pass of the solve.  Problem p = records off[p * off_stride] ..
+// off[p * off_stride + 1] (stride 1: loam_vo_solve's running offsets; 2: a [begin, end) pair per
+// problem, as k_vo_assemble writes them)
+__global__ void __launch_bounds__(VO_THREADS) k_vo_solve(const double* factors, const int* off, int off_stride,
+                                                          double* xs, int max_iter, loam_lm_stats* stats) {
   __shared__ LmState S;
   __shared__ double sum[LM_NACC];
   __shared__ double X[7];
   const int p = blockIdx.x, tid = threadIdx.x, wid = tid >> 6, lane = tid & 63;
-  const int r0 = off[p], nrec = off[p + 1] - r0;
+  const int r0 = off[p * off_stride], nrec = off[p * off_stride + 1] - r0;
   const double* F = factors + (size_t)r0 * 10;
   if (tid == 0) {
     double x7[7] = {xs[6 * p], xs[6 * p + 1], xs[6 * p + 2], xs[6 * p + 3], xs[6 * p + 4], xs[6 * p + 5], 0.0};
@@ -193,8 +199,24 @@ __global__ void __launch_bounds__(VO_THREADS) k_vo_solve(const double* factors, 
   if (tid == 0) {
     if (S.status != LM_DONE) S.term = 5;  // pass budget exhausted (not reached with <= 100 iterations)
     for (int i = 0; i < 6; ++i) xs[6 * p + i] = S.best[i];
-    states[p] = S;
+    loam_lm_stats st;
+    st.iterations = S.iteration;
+    st.successful = S.successful;
+    st.invalid = S.invalid;
+    st.termination = S.term;
+    st.initial_cost = S.initial_cost;
+    st.final_cost = S.min_cost;
+    stats[p] = st;
   }
+}
+
+int32_t vo_solve_launch(const double* d_records, const int* d_off, int off_stride, double* d_x, int max_iterations,
+                        loam_lm_stats* d_stats, int n_problems, hipStream_t st) {
+  if (max_iterations < 0 || max_iterations > VO_MAX_ITERATIONS) return LOAM_ERR_ARG;
+  if (n_problems <= 0) return LOAM_OK;
+  k_vo_solve<<<n_problems, VO_THREADS, 0, st>>>(d_records, d_off, off_stride, d_x, max_iterations, d_stats);
+  LOAM_HIP(hipGetLastError());
+  return LOAM_OK;
 }
 
 }  // namespace loam
@@ -206,7 +228,7 @@ extern "C" {
 int32_t loam_vo_solve(int32_t device, int32_t n_problems, const int32_t* offsets, const double* factors,
                       double* x, int32_t max_iterations, loam_lm_stats* st) {
   if (n_problems < 0 || (n_problems > 0 && (!offsets || !x)) || max_iterations < 0 ||
-      max_iterations > VO_MAX_PASSES - 1) {
+      max_iterations > VO_MAX_ITERATIONS) {
     set_error("loam_vo_solve: bad arguments");
     return LOAM_ERR_ARG;
   }
@@ -223,7 +245,7 @@ int32_t loam_vo_solve(int32_t device, int32_t n_problems, const int32_t* offsets
   double* d_f = nullptr;
   double* d_x = nullptr;
   int* d_off = nullptr;
-  LmState* d_s = nullptr;
+  loam_lm_stats* d_s = nullptr;
   auto cleanup = [&]() {
     if (d_f) (void)hipFree(d_f);
     if (d_x) (void)hipFree(d_x);
@@ -233,32 +255,24 @@ int32_t loam_vo_solve(int32_t device, int32_t n_problems, const int32_t* offsets
   hipError_t e = hipMalloc(&d_f, sizeof(double) * 10 * std::max(nf, 1));
   if (e == hipSuccess) e = hipMalloc(&d_x, sizeof(double) * 6 * n_problems);
   if (e == hipSuccess) e = hipMalloc(&d_off, sizeof(int) * (n_problems + 1));
-  if (e == hipSuccess) e = hipMalloc(&d_s, sizeof(LmState) * n_problems);
+  if (e == hipSuccess) e = hipMalloc(&d_s, sizeof(loam_lm_stats) * n_problems);
   if (e == hipSuccess && nf) e = hipMemcpy(d_f, factors, sizeof(double) * 10 * nf, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(d_x, x, sizeof(double) * 6 * n_problems, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(d_off, offsets, sizeof(int) * (n_problems + 1), hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    k_vo_solve<<<n_problems, VO_THREADS>>>(d_f, d_off, d_x, max_iterations, d_s);
-    e = hipGetLastError();
+  int32_t launched = LOAM_OK;  // a failed launch has set the error text itself
+  if (e == hipSuccess) launched = vo_solve_launch(d_f, d_off, 1, d_x, max_iterations, d_s, n_problems, nullptr);
+  if (launched != LOAM_OK) {
+    cleanup();
+    return launched;
   }
   if (e == hipSuccess) e = hipDeviceSynchronize();
   if (e == hipSuccess) e = hipMemcpy(x, d_x, sizeof(double) * 6 * n_problems, hipMemcpyDeviceToHost);
-  std::vector<LmState> hs(n_problems);
-  if (e == hipSuccess) e = hipMemcpy(hs.data(), d_s, sizeof(LmState) * n_problems, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && st) e = hipMemcpy(st, d_s, sizeof(loam_lm_stats) * n_problems, hipMemcpyDeviceToHost);
   cleanup();
   if (e != hipSuccess) {
     set_error(std::string("loam_vo_solve: ") + hipGetErrorString(e));
     return LOAM_ERR_HIP;
   }
-  if (st)
-    for (int p = 0; p < n_problems; ++p) {
-      st[p].iterations = hs[p].iteration;
-      st[p].successful = hs[p].successful;
-      st[p].invalid = hs[p].invalid;
-      st[p].termination = hs[p].term;
-      st[p].initial_cost = hs[p].initial_cost;
-      st[p].final_cost = hs[p].min_cost;
-    }
   return LOAM_OK;
 }
 

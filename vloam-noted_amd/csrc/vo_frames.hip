@@ -1,0 +1,646 @@
+// vo_frames.hip — the visual-odometry frame between the descriptors and the pose, on MI355X.
+//
+// Reference: VisualOdometry::solveNlsAll (src/visual_odometry/src/visual_odometry.cpp:304-509)
+// with the matcher it is handed, ImageUtil::matchDescriptors (image_util.cpp:347-438: ORB,
+// BFMatcher(NORM_HAMMING), knnMatch k = 2, ratio 0.8).  One handle = n_pairs independent frame
+// pairs; one launch sequence per loam_vo_frames_solve for all of them, nothing read back between:
+//   k_vo_match     Hamming brute force: one query descriptor per lane (in VGPRs), the train
+//                  descriptors staged through LDS in tiles every lane reads at the same address
+//                  (a broadcast), the train set cut into S slices over grid.y so that one pair
+//                  still fills the chip; grid.z = the pair.  Writes (best, its index, second
+//                  best) per (slice, query).
+//   k_vo_merge     one workgroup per pair: merges the slices exactly (the second best is the
+//                  smallest of every slice's second best and every losing slice's best), applies
+//                  the ratio test in double as the reference does, and compacts the accepted
+//                  matches stably in query order (ballots).  An accepted match has a strictly
+//                  unique best (match_ratio <= 1), so no index tie ever decides one.  Tracks
+//                  (optical_flow_match): the points with status 1, as (j, j, 0).
+//   k_vo_assemble  one workgroup per pair, one thread per match: integer pixel coordinates and
+//                  the outlier gate (:344-368), queryDepth of the previous point (dp_query_one,
+//                  the body loam_depth_query runs), the CostFunctor32 / 22 record (:400-474),
+//                  stable compaction: the record order is the solve's summation order.  Writes the
+//                  pair's record range for the solve.
+//   k_vo_solve     (vo.hip) one workgroup per pair on those records.
+// No workgroup waits on another: the merge is a launch of its own.
+//
+// Records: the right-hand sides are formed in float as the reference does, the 3 x 3 solve with
+// K = P_rect0.leftCols(3) runs in fp64 (an LU with partial pivoting, factored once on the host),
+// the solution is rounded to fp32 (point_3d_rect0_* are Vector3f) and the quotients are fp64:
+// vo.vo_factors' definition (the reference's float colPivHouseholderQr is not pinned).
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "common.h"
+#include "depth_dev.h"
+#include "vo_dev.h"
+
+namespace loam {
+
+constexpr int VM_THREADS = 256;   // k_vo_match: queries per workgroup
+constexpr int VM_TILE = 256;      // train descriptors per LDS tile
+constexpr int VM_INF = 1 << 20;   // "no neighbour yet" (a distance is <= 512)
+constexpr int VM_MAX_SLICES = 16;
+constexpr int VA_THREADS = 1024;  // k_vo_merge / k_vo_assemble: one workgroup per pair
+constexpr int VF_MAX_KEYPOINTS = 1 << 16;
+
+enum { VF_NONE = 0, VF_DESC = 1, VF_TRACKS = 2 };
+
+struct VfPair {
+  int mode;    // VF_*: what the pair's pending input is
+  int n0, n1;  // descriptors of image 0 / 1 (tracks: n0 = n1 = n)
+  int stream;  // depth stream of the previous frame
+};
+
+struct VfCount {
+  int n_knn, n_matches, n_gated, counter32, counter22;
+};
+
+struct VfCam {
+  double lu[9];  // P K = L U (unit L below the diagonal, U on and above), row-major
+  int perm[3];
+};
+
+// exclusive rank of the threads with keep set, in thread order, and their number (every thread
+// of the workgroup calls it)
+__device__ inline int vf_block_rank(bool keep, int* ws, int* total) {
+  const int tid = threadIdx.x, wid = tid >> 6;
+  const uint64_t bal = __ballot(keep);
+  if ((tid & 63) == 0) ws[wid] = __popcll(bal);
+  __syncthreads();
+  int off = 0, tot = 0;
+  for (int w = 0; w < (int)blockDim.x / 64; ++w) {
+    const int v = ws[w];
+    if (w < wid) off += v;
+    tot += v;
+  }
+  __syncthreads();
+  *total = tot;
+  return off + __popcll(bal & lanemask_lt());
+}
+
+// WP: dwords per stored descriptor (8 or 16; shorter ones are zero-padded, which adds no bits)
+template <int WP>
+__global__ void __launch_bounds__(VM_THREADS) k_vo_match(const VfPair* pairs, const uint32_t* desc0,
+                                                         const uint32_t* desc1, int K, int S, int3* part) {
+  __shared__ uint4 tile[VM_TILE * WP / 4];
+  const int p = blockIdx.z, s = blockIdx.y, tid = threadIdx.x;
+  const VfPair P = pairs[p];
+  const int q0 = blockIdx.x * VM_THREADS;
+  if (P.mode != VF_DESC || P.n1 < 2 || q0 >= P.n0) return;  // the whole workgroup
+  const int q = q0 + tid;
+  const bool live = q < P.n0;
+  const int ntiles = (P.n1 + VM_TILE - 1) / VM_TILE, tps = (ntiles + S - 1) / S;
+  const int t_begin = min(P.n1, s * tps * VM_TILE), t_end = min(P.n1, (s + 1) * tps * VM_TILE);
+  uint32_t qd[WP];
+  {
+    const uint4* src = reinterpret_cast<const uint4*>(desc0 + ((size_t)p * K + (live ? q : q0)) * WP);
+#pragma unroll
+    for (int k = 0; k < WP / 4; ++k) {
+      const uint4 v = src[k];
+      qd[4 * k] = v.x;
+      qd[4 * k + 1] = v.y;
+      qd[4 * k + 2] = v.z;
+      qd[4 * k + 3] = v.w;
+    }
+  }
+  int d0 = VM_INF, i0 = -1, d1 = VM_INF;
+  for (int t0 = t_begin; t0 < t_end; t0 += VM_TILE) {
+    const int nt = min(VM_TILE, t_end - t0);
+    __syncthreads();
+    const uint4* src = reinterpret_cast<const uint4*>(desc1 + ((size_t)p * K + t0) * WP);
+    for (int i = tid; i < nt * (WP / 4); i += VM_THREADS) tile[i] = src[i];
+    __syncthreads();
+    for (int j = 0; j < nt; ++j) {
+      int d = 0;
+#pragma unroll
+      for (int k = 0; k < WP / 4; ++k) {
+        const uint4 v = tile[j * (WP / 4) + k];  // the same address in every lane
+        d += __popc(qd[4 * k] ^ v.x) + __popc(qd[4 * k + 1] ^ v.y) + __popc(qd[4 * k + 2] ^ v.z) +
+             __popc(qd[4 * k + 3] ^ v.w);
+      }
+      if (d < d1) {
+        if (d < d0) {  // strict: the first of equal bests keeps the index, the other is the second
+          d1 = d0;
+          d0 = d;
+          i0 = t0 + j;
+        } else {
+          d1 = d;
+        }
+      }
+    }
+  }
+  if (live) part[((size_t)p * S + s) * K + q] = make_int3(d0, i0, d1);
+}
+
+__global__ void __launch_bounds__(VA_THREADS) k_vo_merge(const VfPair* pairs, const int3* part, int S, int K,
+                                                         double ratio, const uint8_t* status, int3* matches,
+                                                         VfCount* cnt) {
+  __shared__ int ws[VA_THREADS / 64];
+  const int p = blockIdx.x, tid = threadIdx.x;
+  const VfPair P = pairs[p];
+  if (P.mode == VF_NONE) return;
+  const bool knn = P.mode == VF_DESC && P.n1 >= 2;  // knn_match[1] exists
+  int base = 0;
+  for (int c0 = 0; c0 < P.n0; c0 += VA_THREADS) {
+    const int q = c0 + tid;
+    bool keep = false;
+    int3 m = make_int3(q, q, 0);
+    if (q < P.n0) {
+      if (P.mode == VF_TRACKS) {
+        keep = status[(size_t)p * K + q] == 1;
+      } else if (knn) {
+        int d0 = VM_INF, i0 = -1, d1 = VM_INF;
+        for (int s = 0; s < S; ++s) {
+          const int3 e = part[((size_t)p * S + s) * K + q];
+          if (e.x < d0) {
+            d1 = min(d0, e.z);
+            d0 = e.x;
+            i0 = e.y;
+          } else {
+            d1 = min(d1, e.x);
+          }
+        }
+        // image_util.cpp:417: float < 0.8 * float, evaluated in double
+        keep = (double)d0 < ratio * (double)d1;
+        m = make_int3(q, i0, d0);
+      }
+    }
+    int tot;
+    const int pos = vf_block_rank(keep, ws, &tot);
+    if (keep) matches[(size_t)p * K + base + pos] = m;
+    base += tot;
+  }
+  if (tid == 0) {
+    cnt[p].n_knn = (P.mode == VF_TRACKS || knn) ? P.n0 : 0;
+    cnt[p].n_matches = base;
+  }
+}
+
+// x = K^-1 b through the host's LU
+__device__ inline void vf_solve3(const VfCam& C, const double* b, double* x) {
+  const double y0 = b[C.perm[0]];
+  const double y1 = b[C.perm[1]] - C.lu[3] * y0;
+  const double y2 = (b[C.perm[2]] - C.lu[6] * y0) - C.lu[7] * y1;
+  x[2] = y2 / C.lu[8];
+  x[1] = (y1 - C.lu[5] * x[2]) / C.lu[4];
+  x[0] = ((y0 - C.lu[1] * x[1]) - C.lu[2] * x[2]) / C.lu[0];
+}
+
+// the float image-frame vector (a, b, c) -> point_3d_rect0 (Vector3f)
+__device__ inline void vf_unproject(const VfCam& C, float a, float b, float c, float* out) {
+  const double rhs[3] = {(double)a, (double)b, (double)c};
+  double x[3];
+  vf_solve3(C, rhs, x);
+  for (int i = 0; i < 3; ++i) out[i] = (float)x[i];
+}
+
+__global__ void __launch_bounds__(VA_THREADS) k_vo_assemble(const VfPair* pairs, const int3* matches, VfCount* cnt,
+                                                            const float2* kp0, const float2* kp1, int K, DepthDev D,
+                                                            VfCam cam, int gate, int radius, double* records,
+                                                            float* depth0, int* off) {
+  __shared__ int ws[VA_THREADS / 64];
+  __shared__ int n32;
+  const int p = blockIdx.x, tid = threadIdx.x;
+  const VfPair P = pairs[p];
+  if (tid == 0) {  // an idle pair solves an empty problem
+    off[2 * p] = p * K;
+    off[2 * p + 1] = p * K;
+    n32 = 0;
+  }
+  if (P.mode == VF_NONE) return;
+  __syncthreads();
+  const int nm = cnt[p].n_matches;
+  int base = 0;
+  for (int c0 = 0; c0 < nm; c0 += VA_THREADS) {
+    const int i = c0 + tid;
+    bool keep = false;
+    float d = -1.0f;
+    double rec[10];
+    for (int k = 0; k < 10; ++k) rec[k] = 0.0;
+    if (i < nm) {
+      const int3 m = matches[(size_t)p * K + i];
+      const float2 a = kp0[(size_t)p * K + m.x], b = kp1[(size_t)p * K + m.y];
+      // :344-356: the pixel coordinates are stored in ints
+      const int px = static_cast<int>(a.x), py = static_cast<int>(a.y);
+      const int cx = static_cast<int>(b.x), cy = static_cast<int>(b.y);
+      keep = true;
+      if (gate > 0) {  // :363-368
+        const long long dx = (long long)px - cx, dy = (long long)py - cy;
+        keep = !(dx * dx + dy * dy > (long long)gate * gate);
+      }
+      if (keep) {
+        const float fx = (float)px, fy = (float)py;
+        d = dp_query_one(D, P.stream, fx, fy, radius);  // :371
+        float p1[3];
+        vf_unproject(cam, (float)cx, (float)cy, 1.0f, p1);
+        const double x1 = (double)p1[0] / (double)p1[2], y1 = (double)p1[1] / (double)p1[2];
+        if (d > 0) {  // CostFunctor32, :400-427
+          float X0[3];
+          vf_unproject(cam, fx * d, fy * d, d, X0);
+          rec[0] = 4.0;
+          rec[1] = (double)X0[0];
+          rec[2] = (double)X0[1];
+          rec[3] = (double)X0[2];
+          rec[4] = x1;
+          rec[5] = y1;
+        } else {  // CostFunctor22, :452-474
+          float p0[3];
+          vf_unproject(cam, fx, fy, 1.0f, p0);
+          rec[0] = 5.0;
+          rec[4] = (double)p0[0] / (double)p0[2];
+          rec[5] = (double)p0[1] / (double)p0[2];
+          rec[7] = x1;
+          rec[8] = y1;
+        }
+      }
+    }
+    int tot;
+    const int pos = vf_block_rank(keep, ws, &tot);
+    if (keep) {
+      const size_t r = (size_t)p * K + base + pos;
+      for (int k = 0; k < 10; ++k) records[r * 10 + k] = rec[k];
+      depth0[r] = d;
+    }
+    const uint64_t has = __ballot(keep && d > 0);
+    if ((tid & 63) == 0 && has) atomicAdd(&n32, __popcll(has));
+    base += tot;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    off[2 * p + 1] = p * K + base;
+    cnt[p].n_gated = base;
+    cnt[p].counter32 = n32;
+    cnt[p].counter22 = base - n32;
+  }
+}
+
+}  // namespace loam
+
+using namespace loam;
+
+struct loam_vo_frames {
+  int dev = 0;
+  int P = 0, K = 0;       // pairs, keypoints per image
+  int W = 0, WP = 0;      // descriptor dwords given / stored
+  int S_cap = 1;          // slices the partial buffer holds
+  loam_vo_frames_params prm{};
+  loam_depth* depth = nullptr;
+  VfCam cam{};
+  std::vector<VfPair> pairs;    // pending inputs
+  std::vector<char> solved;     // the pair has results
+  std::vector<double> x0, x;    // [P][6] initial values / results
+  std::vector<loam_lm_stats> lm;
+  std::vector<VfCount> cnt;
+  std::vector<void*> allocs;
+  VfPair* d_pairs = nullptr;
+  uint32_t *d_desc0 = nullptr, *d_desc1 = nullptr;  // [P][K][WP]
+  float2 *d_kp0 = nullptr, *d_kp1 = nullptr;        // [P][K]
+  uint8_t* d_status = nullptr;                      // [P][K]
+  int3* d_part = nullptr;                           // [P][S_cap][K]
+  int3* d_matches = nullptr;                        // [P][K]
+  double* d_records = nullptr;                      // [P][K][10]
+  float* d_depth0 = nullptr;                        // [P][K]
+  int* d_off = nullptr;                             // [P][2]
+  double* d_x = nullptr;                            // [P][6]
+  loam_lm_stats* d_lm = nullptr;
+  VfCount* d_cnt = nullptr;
+  hipStream_t st = nullptr;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  float ms = 0.f;
+};
+
+namespace {
+
+template <typename T>
+int32_t vf_alloc(loam_vo_frames* h, T** p, size_t n) {
+  void* q = nullptr;
+  const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
+  LOAM_HIP(hipMalloc(&q, bytes));
+  LOAM_HIP(hipMemsetAsync(q, 0, bytes, h->st));
+  h->allocs.push_back(q);
+  *p = reinterpret_cast<T*>(q);
+  return LOAM_OK;
+}
+
+void vf_free(loam_vo_frames* h) {
+  for (void* p : h->allocs) (void)hipFree(p);
+  h->allocs.clear();
+  for (auto& e : h->ev)
+    if (e) (void)hipEventDestroy(e);
+  if (h->st) (void)hipStreamDestroy(h->st);
+}
+
+// P K = L U with partial pivoting; false when K is singular to working precision
+bool vf_factor(const float* P_rect0, VfCam* C) {
+  double a[9];
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) a[3 * i + j] = (double)P_rect0[4 * i + j];
+  double scale = 0.0;
+  for (double v : a) scale = std::max(scale, std::fabs(v));
+  if (!(scale > 0.0) || !std::isfinite(scale)) return false;
+  int perm[3] = {0, 1, 2};
+  for (int c = 0; c < 3; ++c) {
+    int piv = c;
+    for (int r = c + 1; r < 3; ++r)
+      if (std::fabs(a[3 * r + c]) > std::fabs(a[3 * piv + c])) piv = r;
+    if (!(std::fabs(a[3 * piv + c]) > 1e-12 * scale)) return false;
+    if (piv != c) {
+      for (int j = 0; j < 3; ++j) std::swap(a[3 * c + j], a[3 * piv + j]);
+      std::swap(perm[c], perm[piv]);
+    }
+    for (int r = c + 1; r < 3; ++r) {
+      a[3 * r + c] /= a[3 * c + c];
+      for (int j = c + 1; j < 3; ++j) a[3 * r + j] -= a[3 * r + c] * a[3 * c + j];
+    }
+  }
+  for (int i = 0; i < 9; ++i) C->lu[i] = a[i];
+  for (int i = 0; i < 3; ++i) C->perm[i] = perm[i];
+  return true;
+}
+
+int32_t vf_check(loam_vo_frames* h, int32_t pair, const char* who) {
+  if (!h || pair < 0 || pair >= h->P) {
+    set_error(std::string(who) + ": bad handle or pair");
+    return LOAM_ERR_ARG;
+  }
+  return LOAM_OK;
+}
+
+int32_t vf_check_input(loam_vo_frames* h, int32_t pair, int32_t n0, int32_t n1, int32_t stream, const char* who) {
+  TRY(vf_check(h, pair, who));
+  DepthDev D;
+  int dev;
+  TRY(depth_device_view(h->depth, &D, &dev));
+  if (n0 < 0 || n1 < 0 || stream < 0 || stream >= D.B) {
+    set_error(std::string(who) + ": bad sizes or depth stream");
+    return LOAM_ERR_ARG;
+  }
+  if (n0 > h->K || n1 > h->K) {
+    set_error(std::string(who) + ": more keypoints than max_keypoints");
+    return LOAM_ERR_CAPACITY;
+  }
+  return LOAM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void loam_vo_frames_params_default(loam_vo_frames_params* p) {
+  if (!p) return;
+  *p = loam_vo_frames_params{};
+  p->remove_vo_outlier = 100;
+  p->match_ratio = 0.8;
+  p->desc_bytes = 32;
+  p->depth_radius = 2;
+  p->max_iterations = 100;
+  p->max_keypoints = 8192;
+}
+
+int32_t loam_vo_frames_create(const loam_vo_frames_params* p, loam_depth* depth, int32_t n_pairs,
+                              loam_vo_frames** out) {
+  if (!out || !p || !depth || n_pairs <= 0 || p->desc_bytes < 4 || p->desc_bytes > 64 || p->desc_bytes % 4 != 0 ||
+      !(p->match_ratio > 0.0 && p->match_ratio <= 1.0) || p->depth_radius < 0 || p->max_iterations < 0 ||
+      p->max_iterations > VO_MAX_ITERATIONS || p->max_keypoints <= 0 || p->max_keypoints > VF_MAX_KEYPOINTS ||
+      (int64_t)n_pairs * p->max_keypoints > (int64_t)1 << 28) {
+    set_error("loam_vo_frames_create: bad arguments");
+    return LOAM_ERR_ARG;
+  }
+  *out = nullptr;
+  VfCam cam;
+  if (!vf_factor(p->P_rect0, &cam)) {
+    set_error("loam_vo_frames_create: P_rect0.leftCols(3) is singular");
+    return LOAM_ERR_ARG;
+  }
+  DepthDev D;
+  int dev = 0;
+  TRY(depth_device_view(depth, &D, &dev));
+  LOAM_HIP(hipSetDevice(dev));
+  auto* h = new loam_vo_frames;
+  h->dev = dev;
+  h->depth = depth;
+  h->prm = *p;
+  h->cam = cam;
+  h->P = n_pairs;
+  h->K = p->max_keypoints;
+  h->W = p->desc_bytes / 4;
+  h->WP = h->W <= 8 ? 8 : 16;
+  h->S_cap = std::max(1, std::min(VM_MAX_SLICES, 256 / n_pairs));
+  auto fail = [&](int32_t r) {
+    vf_free(h);
+    delete h;
+    return r;
+  };
+  if (hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking) != hipSuccess) return fail(LOAM_ERR_HIP);
+  for (auto& e : h->ev)
+    if (hipEventCreate(&e) != hipSuccess) return fail(LOAM_ERR_HIP);
+  const size_t P = n_pairs, K = h->K;
+  int32_t rc = LOAM_OK;
+#define VA(ptr, n) \
+  if ((rc = vf_alloc(h, &(ptr), (n))) != LOAM_OK) return fail(rc)
+  VA(h->d_pairs, P);
+  VA(h->d_desc0, P * K * h->WP);
+  VA(h->d_desc1, P * K * h->WP);
+  VA(h->d_kp0, P * K);
+  VA(h->d_kp1, P * K);
+  VA(h->d_status, P * K);
+  VA(h->d_part, P * h->S_cap * K);
+  VA(h->d_matches, P * K);
+  VA(h->d_records, P * K * 10);
+  VA(h->d_depth0, P * K);
+  VA(h->d_off, P * 2);
+  VA(h->d_x, P * 6);
+  VA(h->d_lm, P);
+  VA(h->d_cnt, P);
+#undef VA
+  h->pairs.assign(P, VfPair{});
+  h->solved.assign(P, 0);
+  h->x0.assign(P * 6, 0.0);
+  h->x.assign(P * 6, 0.0);
+  h->lm.assign(P, loam_lm_stats{});
+  h->cnt.assign(P, VfCount{});
+  if (hipStreamSynchronize(h->st) != hipSuccess) return fail(LOAM_ERR_HIP);
+  *out = h;
+  return LOAM_OK;
+}
+
+int32_t loam_vo_frames_destroy(loam_vo_frames* h) {
+  if (!h) return LOAM_ERR_ARG;
+  (void)hipSetDevice(h->dev);
+  vf_free(h);
+  delete h;
+  return LOAM_OK;
+}
+
+int32_t loam_vo_frames_input_descriptors(loam_vo_frames* h, int32_t pair, const float* kp0_xy,
+                                         const uint8_t* desc0, int32_t n0, const float* kp1_xy,
+                                         const uint8_t* desc1, int32_t n1, int32_t depth_stream_prev) {
+  const char* who = "loam_vo_frames_input_descriptors";
+  TRY(vf_check_input(h, pair, n0, n1, depth_stream_prev, who));
+  if ((n0 > 0 && (!kp0_xy || !desc0)) || (n1 > 0 && (!kp1_xy || !desc1))) {
+    set_error(std::string(who) + ": null input");
+    return LOAM_ERR_ARG;
+  }
+  LOAM_HIP(hipSetDevice(h->dev));
+  const size_t o = (size_t)pair * h->K, row = sizeof(uint32_t) * h->W, pitch = sizeof(uint32_t) * h->WP;
+  // rows are stored WP dwords apart; the padding stays zero from create
+  if (n0) {
+    LOAM_HIP(hipMemcpy2DAsync(h->d_desc0 + o * h->WP, pitch, desc0, row, row, n0, hipMemcpyHostToDevice, h->st));
+    LOAM_HIP(hipMemcpyAsync(h->d_kp0 + o, kp0_xy, sizeof(float2) * n0, hipMemcpyHostToDevice, h->st));
+  }
+  if (n1) {
+    LOAM_HIP(hipMemcpy2DAsync(h->d_desc1 + o * h->WP, pitch, desc1, row, row, n1, hipMemcpyHostToDevice, h->st));
+    LOAM_HIP(hipMemcpyAsync(h->d_kp1 + o, kp1_xy, sizeof(float2) * n1, hipMemcpyHostToDevice, h->st));
+  }
+  LOAM_HIP(hipStreamSynchronize(h->st));  // the caller's buffers are free after return
+  h->pairs[pair] = VfPair{VF_DESC, n0, n1, depth_stream_prev};
+  return LOAM_OK;
+}
+
+int32_t loam_vo_frames_input_tracks(loam_vo_frames* h, int32_t pair, const float* prev_xy, const float* curr_xy,
+                                    const uint8_t* status, int32_t n, int32_t depth_stream_prev) {
+  const char* who = "loam_vo_frames_input_tracks";
+  TRY(vf_check_input(h, pair, n, n, depth_stream_prev, who));
+  if (n > 0 && (!prev_xy || !curr_xy || !status)) {
+    set_error(std::string(who) + ": null input");
+    return LOAM_ERR_ARG;
+  }
+  LOAM_HIP(hipSetDevice(h->dev));
+  const size_t o = (size_t)pair * h->K;
+  if (n) {
+    LOAM_HIP(hipMemcpyAsync(h->d_kp0 + o, prev_xy, sizeof(float2) * n, hipMemcpyHostToDevice, h->st));
+    LOAM_HIP(hipMemcpyAsync(h->d_kp1 + o, curr_xy, sizeof(float2) * n, hipMemcpyHostToDevice, h->st));
+    LOAM_HIP(hipMemcpyAsync(h->d_status + o, status, (size_t)n, hipMemcpyHostToDevice, h->st));
+  }
+  LOAM_HIP(hipStreamSynchronize(h->st));
+  h->pairs[pair] = VfPair{VF_TRACKS, n, n, depth_stream_prev};
+  return LOAM_OK;
+}
+
+int32_t loam_vo_frames_set_initial(loam_vo_frames* h, int32_t pair, const double* x6) {
+  TRY(vf_check(h, pair, "loam_vo_frames_set_initial"));
+  for (int i = 0; i < 6; ++i) h->x0[(size_t)pair * 6 + i] = x6 ? x6[i] : 0.0;
+  return LOAM_OK;
+}
+
+int32_t loam_vo_frames_solve(loam_vo_frames* h) {
+  if (!h) return LOAM_ERR_ARG;
+  int active = 0, max_n0 = 0, max_n1 = 0;
+  bool match = false;
+  for (const VfPair& p : h->pairs) {
+    if (p.mode == VF_NONE) continue;
+    ++active;
+    if (!depth_stream_processed(h->depth, p.stream)) {
+      set_error("loam_vo_frames_solve: depth stream " + std::to_string(p.stream) + " was never processed");
+      return LOAM_ERR_STATE;
+    }
+    if (p.mode == VF_DESC && p.n0 > 0 && p.n1 >= 2) {
+      match = true;
+      max_n0 = std::max(max_n0, p.n0);
+      max_n1 = std::max(max_n1, p.n1);
+    }
+  }
+  if (!active) {
+    set_error("loam_vo_frames_solve: no pair has an input");
+    return LOAM_ERR_STATE;
+  }
+  DepthDev D;
+  int dev;
+  TRY(depth_device_view(h->depth, &D, &dev));
+  LOAM_HIP(hipSetDevice(h->dev));
+  hipStream_t st = h->st;
+  const int P = h->P, K = h->K;
+  // slices of the train set: enough workgroups for two per CU, no slice thinner than a tile
+  const int qb = (max_n0 + VM_THREADS - 1) / VM_THREADS, tiles = (max_n1 + VM_TILE - 1) / VM_TILE;
+  int S = 1;
+  if (match) S = std::max(1, std::min({h->S_cap, tiles, (512 + qb * active - 1) / (qb * active)}));
+  LOAM_HIP(hipMemcpyAsync(h->d_pairs, h->pairs.data(), sizeof(VfPair) * P, hipMemcpyHostToDevice, st));
+  LOAM_HIP(hipMemcpyAsync(h->d_x, h->x0.data(), sizeof(double) * 6 * P, hipMemcpyHostToDevice, st));
+  LOAM_HIP(hipEventRecord(h->ev[0], st));
+  if (match) {
+    const dim3 grid(qb, S, P);
+    if (h->WP == 8)
+      k_vo_match<8><<<grid, VM_THREADS, 0, st>>>(h->d_pairs, h->d_desc0, h->d_desc1, K, S, h->d_part);
+    else
+      k_vo_match<16><<<grid, VM_THREADS, 0, st>>>(h->d_pairs, h->d_desc0, h->d_desc1, K, S, h->d_part);
+  }
+  k_vo_merge<<<P, VA_THREADS, 0, st>>>(h->d_pairs, h->d_part, S, K, h->prm.match_ratio, h->d_status, h->d_matches,
+                                       h->d_cnt);
+  k_vo_assemble<<<P, VA_THREADS, 0, st>>>(h->d_pairs, h->d_matches, h->d_cnt, h->d_kp0, h->d_kp1, K, D, h->cam,
+                                          h->prm.remove_vo_outlier, h->prm.depth_radius, h->d_records, h->d_depth0,
+                                          h->d_off);
+  LOAM_HIP(hipGetLastError());
+  TRY(vo_solve_launch(h->d_records, h->d_off, 2, h->d_x, h->prm.max_iterations, h->d_lm, P, st));
+  LOAM_HIP(hipEventRecord(h->ev[1], st));
+  std::vector<double> x(6 * (size_t)P);
+  std::vector<loam_lm_stats> lm(P);
+  std::vector<VfCount> cnt(P);
+  LOAM_HIP(hipMemcpyAsync(x.data(), h->d_x, sizeof(double) * 6 * P, hipMemcpyDeviceToHost, st));
+  LOAM_HIP(hipMemcpyAsync(lm.data(), h->d_lm, sizeof(loam_lm_stats) * P, hipMemcpyDeviceToHost, st));
+  LOAM_HIP(hipMemcpyAsync(cnt.data(), h->d_cnt, sizeof(VfCount) * P, hipMemcpyDeviceToHost, st));
+  LOAM_HIP(hipStreamSynchronize(st));
+  LOAM_HIP(hipEventElapsedTime(&h->ms, h->ev[0], h->ev[1]));
+  for (int p = 0; p < P; ++p) {
+    if (h->pairs[p].mode == VF_NONE) continue;  // an idle pair keeps its earlier results
+    for (int i = 0; i < 6; ++i) h->x[6 * (size_t)p + i] = x[6 * (size_t)p + i];
+    h->lm[p] = lm[p];
+    h->cnt[p] = cnt[p];
+    h->solved[p] = 1;
+    h->pairs[p].mode = VF_NONE;
+  }
+  return LOAM_OK;
+}
+
+int32_t loam_vo_frames_result(loam_vo_frames* h, int32_t pair, double* x6, loam_lm_stats* lm,
+                              loam_vo_frame_stats* st) {
+  TRY(vf_check(h, pair, "loam_vo_frames_result"));
+  if (!h->solved[pair]) {
+    set_error("loam_vo_frames_result: the pair was never solved");
+    return LOAM_ERR_STATE;
+  }
+  if (x6)
+    for (int i = 0; i < 6; ++i) x6[i] = h->x[(size_t)pair * 6 + i];
+  if (lm) *lm = h->lm[pair];
+  if (st) {
+    const VfCount& c = h->cnt[pair];
+    st->n_knn = c.n_knn;
+    st->n_matches = c.n_matches;
+    st->n_gated = c.n_gated;
+    st->counter32 = c.counter32;
+    st->counter22 = c.counter22;
+    st->ms = (double)h->ms;
+  }
+  return LOAM_OK;
+}
+
+int32_t loam_vo_frames_matches_copy(loam_vo_frames* h, int32_t pair, int32_t* out, int32_t cap) {
+  TRY(vf_check(h, pair, "loam_vo_frames_matches_copy"));
+  if (!h->solved[pair]) {
+    set_error("loam_vo_frames_matches_copy: the pair has no solved frame");
+    return LOAM_ERR_STATE;
+  }
+  const int n = h->cnt[pair].n_matches;
+  if (n > cap || n == 0 || !out) return n;  // the count only
+  LOAM_HIP(hipSetDevice(h->dev));
+  LOAM_HIP(hipMemcpy(out, h->d_matches + (size_t)pair * h->K, sizeof(int3) * n, hipMemcpyDeviceToHost));
+  return n;
+}
+
+int32_t loam_vo_frames_records_copy(loam_vo_frames* h, int32_t pair, double* records, float* depth0,
+                                    int32_t cap) {
+  TRY(vf_check(h, pair, "loam_vo_frames_records_copy"));
+  if (!h->solved[pair]) {
+    set_error("loam_vo_frames_records_copy: the pair has no solved frame");
+    return LOAM_ERR_STATE;
+  }
+  const int n = h->cnt[pair].n_gated;
+  if (n > cap || n == 0) return n;  // the count only
+  LOAM_HIP(hipSetDevice(h->dev));
+  const size_t o = (size_t)pair * h->K;
+  if (records) LOAM_HIP(hipMemcpy(records, h->d_records + o * 10, sizeof(double) * 10 * n, hipMemcpyDeviceToHost));
+  if (depth0) LOAM_HIP(hipMemcpy(depth0, h->d_depth0 + o, sizeof(float) * n, hipMemcpyDeviceToHost));
+  return n;
+}
+
+}  // extern "C"

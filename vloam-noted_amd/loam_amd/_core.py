@@ -59,6 +59,17 @@ class DepthParams(ctypes.Structure):
                 ("grid", c_i32), ("img_width", c_i32), ("img_height", c_i32), ("max_points", c_i32)]
 
 
+class VOFramesParams(ctypes.Structure):
+    _fields_ = [("P_rect0", c_f * 12), ("remove_vo_outlier", c_i32), ("match_ratio", c_d),
+                ("desc_bytes", c_i32), ("depth_radius", c_i32), ("max_iterations", c_i32),
+                ("max_keypoints", c_i32)]
+
+
+class VOFrameStats(ctypes.Structure):
+    _fields_ = [("n_knn", c_i32), ("n_matches", c_i32), ("n_gated", c_i32), ("counter32", c_i32),
+                ("counter22", c_i32), ("ms", c_d)]
+
+
 KFAM = ("stack_voxelgrid", "submap_hash_build", "correspondence", "lm_pass", "insert",
         "cube_revoxel", "other")
 
@@ -152,6 +163,16 @@ SIGNATURES = {
     "loam_depth_query_device": (c_i32, [vp, c_i32, vp, vp, c_i32, vp]),
     "loam_depth_ms": (c_d, [vp]),
     "loam_vo_solve": (c_i32, [c_i32, c_i32, vp, vp, vp, c_i32, vp]),
+    "loam_vo_frames_params_default": (None, [ctypes.POINTER(VOFramesParams)]),
+    "loam_vo_frames_create": (c_i32, [ctypes.POINTER(VOFramesParams), vp, c_i32, ctypes.POINTER(vp)]),
+    "loam_vo_frames_destroy": (c_i32, [vp]),
+    "loam_vo_frames_input_descriptors": (c_i32, [vp, c_i32, vp, vp, c_i32, vp, vp, c_i32, c_i32]),
+    "loam_vo_frames_input_tracks": (c_i32, [vp, c_i32, vp, vp, vp, c_i32, c_i32]),
+    "loam_vo_frames_set_initial": (c_i32, [vp, c_i32, vp]),
+    "loam_vo_frames_solve": (c_i32, [vp]),
+    "loam_vo_frames_result": (c_i32, [vp, c_i32, vp, ctypes.POINTER(LMStats), ctypes.POINTER(VOFrameStats)]),
+    "loam_vo_frames_matches_copy": (c_i32, [vp, c_i32, vp, c_i32]),
+    "loam_vo_frames_records_copy": (c_i32, [vp, c_i32, vp, vp, c_i32]),
     "loam_lm_solve": (c_i32, [c_i32, vp, c_i32, vp, c_i32, ctypes.POINTER(LMStats)]),
     "loam_lm_normal_equations": (c_i32, [c_i32, vp, c_i32, vp, vp, vp, vp]),
     "loam_voxel_grid": (c_i32, [c_i32, vp, c_i32, c_f, vp, ctypes.POINTER(c_i32)]),

@@ -7,6 +7,11 @@ CostFunctor32 (3D point in rectified camera 0 -> normalised image point), otherw
 CostFunctor22 (epipolar).  ``solve`` runs any number of such problems on the device (one
 workgroup per problem, every Ceres iteration on the GPU): HuberLoss(0.1), TR-LM, DENSE_QR,
 max_num_iterations = 100 (:70-74).
+
+``VOFrames`` is the whole frame on the device: descriptors (or LK tracks) in, pose out, with the
+matcher, the gate, the depth lookup and the records between them (``vo_factors`` stays the host
+definition the device records are checked against).  ``vo_to_velo_prior`` turns its solution into
+the prior of the coupled LiDAR odometry.
 """
 import ctypes
 
@@ -64,3 +69,136 @@ def solve(problems, x0=None, max_iterations=100, device=0):
     st = (_core.LMStats * max(P, 1))()
     check(lib().loam_vo_solve(device, P, ptr(off), ptr(F), ptr(x), max_iterations, st))
     return x, [st[i] for i in range(P)]
+
+
+def vo_frames_params(P_rect0=None, **kw):
+    """loam_vo_frames_params: the reference's defaults (remove_vo_outlier 100, match_ratio 0.8,
+    ORB's 32-byte descriptors, searching_radius 2, 100 iterations, 8192 keypoints per image)"""
+    if P_rect0 is None:
+        from .depth import KITTI_P_RECT0 as P_rect0
+    p = _core.VOFramesParams()
+    lib().loam_vo_frames_params_default(ctypes.byref(p))
+    p.P_rect0[:] = [float(v) for v in np.ascontiguousarray(P_rect0, dtype=np.float32).reshape(12)]
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+class VOFrames:
+    """The VO frame on the device (loam_vo_frames_*): ``n_pairs`` independent frame pairs, each
+    from its descriptors (or LK tracks) to angles_0to1 / t_0to1 in one launch sequence per
+    ``solve``: ImageUtil::matchDescriptors, the outlier gate, queryDepth on ``depth`` (a
+    ``BatchDepth`` whose streams hold the previous frames' buckets), the CostFunctor32 / 22
+    records and the Ceres solve of VisualOdometry::solveNlsAll."""
+
+    def __init__(self, depth, n_pairs=1, params=None, **kw):
+        self.params = params if params is not None else vo_frames_params(
+            kw.pop("P_rect0", np.array(depth.params.P_rect0[:], dtype=np.float32)), **kw)
+        self.depth = depth  # the depth handle must outlive this one
+        self.n_pairs = n_pairs
+        h = ctypes.c_void_p()
+        check(lib().loam_vo_frames_create(ctypes.byref(self.params), depth.h, n_pairs, ctypes.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            lib().loam_vo_frames_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def input_descriptors(self, pair, kp0_xy, desc0, kp1_xy, desc1, depth_stream_prev=0):
+        """previous (0) / current (1) image: keypoint pixels (n, 2) and descriptors (n, desc_bytes)"""
+        nb = self.params.desc_bytes
+        k0 = np.ascontiguousarray(kp0_xy, dtype=np.float32).reshape(-1, 2)
+        k1 = np.ascontiguousarray(kp1_xy, dtype=np.float32).reshape(-1, 2)
+        d0 = np.ascontiguousarray(desc0, dtype=np.uint8).reshape(-1, nb)
+        d1 = np.ascontiguousarray(desc1, dtype=np.uint8).reshape(-1, nb)
+        if len(k0) != len(d0) or len(k1) != len(d1):
+            raise ValueError("one keypoint per descriptor")
+        check(lib().loam_vo_frames_input_descriptors(self.h, pair, ptr(k0), ptr(d0), len(d0), ptr(k1), ptr(d1),
+                                                     len(d1), depth_stream_prev))
+
+    def input_tracks(self, pair, prev_xy, curr_xy, status, depth_stream_prev=0):
+        """optical_flow_match: paired points and the LK status (kept where 1)"""
+        a = np.ascontiguousarray(prev_xy, dtype=np.float32).reshape(-1, 2)
+        b = np.ascontiguousarray(curr_xy, dtype=np.float32).reshape(-1, 2)
+        s = np.ascontiguousarray(status, dtype=np.uint8).reshape(-1)
+        if not len(a) == len(b) == len(s):
+            raise ValueError("prev_xy, curr_xy and status must have one row per track")
+        check(lib().loam_vo_frames_input_tracks(self.h, pair, ptr(a), ptr(b), ptr(s), len(s), depth_stream_prev))
+
+    def set_initial(self, pair, x6=None):
+        x = None if x6 is None else np.ascontiguousarray(x6, dtype=np.float64).reshape(6)
+        check(lib().loam_vo_frames_set_initial(self.h, pair, None if x is None else x.ctypes.data))
+
+    def solve(self):
+        check(lib().loam_vo_frames_solve(self.h))
+
+    def result(self, pair=0):
+        """(x6 = angles_0to1 ++ t_0to1, LMStats, VOFrameStats)"""
+        x = np.empty(6)
+        lm, st = _core.LMStats(), _core.VOFrameStats()
+        check(lib().loam_vo_frames_result(self.h, pair, x.ctypes.data, ctypes.byref(lm), ctypes.byref(st)))
+        return x, lm, st
+
+    def matches(self, pair=0):
+        """(n, 3) int32: queryIdx, trainIdx, distance of the accepted matches, in query order"""
+        n = check(lib().loam_vo_frames_matches_copy(self.h, pair, None, 0))
+        out = np.empty((n, 3), dtype=np.int32)
+        if n:
+            check(lib().loam_vo_frames_matches_copy(self.h, pair, ptr(out), n))
+        return out
+
+    def records(self, pair=0):
+        """the residual blocks of the last solve, (n, 10) in ``solve``'s layout, and their depth0"""
+        n = check(lib().loam_vo_frames_records_copy(self.h, pair, None, None, 0))
+        rec, d0 = np.empty((n, 10)), np.empty(n, dtype=np.float32)
+        if n:
+            check(lib().loam_vo_frames_records_copy(self.h, pair, ptr(rec), ptr(d0), n))
+        return rec, d0
+
+
+def vo_to_velo_prior(x6, velo_T_cam0):
+    """velo_last_VOT_velo_curr = velo_T_cam0 . (cam0_curr_T_cam0_last)^-1 . velo_T_cam0^-1
+    (vloam_tf.cpp:66-70) of a VO solution x6 = angles_0to1 ++ t_0to1 (the axis-angle form of
+    visual_odometry.cpp:485-489), as (q_xyzw, t): the argument of loam_odometry_set_prior.
+    None when the angle is 0 (the reference divides by it and guards the NaN, :76-79) or any
+    component is NaN."""
+    x = np.asarray(x6, dtype=np.float64).reshape(6)
+    V = np.asarray(velo_T_cam0, dtype=np.float64).reshape(4, 4)
+    w, t = x[:3], x[3:]
+    angle = np.sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2])
+    if np.isnan(x).any() or np.isnan(V).any() or angle == 0.0:
+        return None
+    u = w / angle
+    Kx = np.array([[0.0, -u[2], u[1]], [u[2], 0.0, -u[0]], [-u[1], u[0], 0.0]])
+    R = np.eye(3) + np.sin(angle) * Kx + (1.0 - np.cos(angle)) * (Kx @ Kx)
+    Tinv = np.eye(4)
+    Tinv[:3, :3] = R.T
+    Tinv[:3, 3] = -R.T @ t
+    Vinv = np.eye(4)
+    Vinv[:3, :3] = V[:3, :3].T
+    Vinv[:3, 3] = -V[:3, :3].T @ V[:3, 3]
+    M = V @ Tinv @ Vinv
+    return _quat_xyzw(M[:3, :3]), M[:3, 3].copy()
+
+
+def _quat_xyzw(R):
+    """unit quaternion (x, y, z, w), w >= 0, of a rotation matrix (largest-component branch)"""
+    q = np.empty(4)
+    tr = R[0, 0] + R[1, 1] + R[2, 2]
+    if tr > 0.0:
+        s = 2.0 * np.sqrt(1.0 + tr)
+        q[:] = (R[2, 1] - R[1, 2]) / s, (R[0, 2] - R[2, 0]) / s, (R[1, 0] - R[0, 1]) / s, 0.25 * s
+    else:
+        i = int(np.argmax(np.diag(R)))
+        j, k = (i + 1) % 3, (i + 2) % 3
+        s = 2.0 * np.sqrt(1.0 + R[i, i] - R[j, j] - R[k, k])
+        q[i], q[j], q[k], q[3] = 0.25 * s, (R[j, i] + R[i, j]) / s, (R[k, i] + R[i, k]) / s, (R[k, j] - R[j, k]) / s
+    q /= np.linalg.norm(q)
+    return q if q[3] >= 0 else -q
