@@ -48,7 +48,8 @@ typedef struct loam_params {
   int32_t mapping_skip_frame;       /* 1 (laser_odometry.cpp:53) */
   int32_t map_pub_number;           /* 20 (laser_mapping.cpp:127) */
   double mapping_line_resolution;   /* 0.4 m (laser_mapping.cpp:99) */
-  double mapping_plane_resolution;  /* 0.8 m (laser_mapping.cpp:101) */
+  double mapping_plane_resolution;  /* 0.8 m (laser_mapping.cpp:101); both leaves finite and > 0,
+                                       else loam_mapper_create returns LOAM_ERR_ARG */
   int32_t detach_vo_lo;             /* 1 (laser_odometry.cpp:47); 0: coupled mode, loam_odometry_set_prior
                                        is required before every solve (:237-250) */
   int32_t verbose_level;            /* loam_verbose_level */

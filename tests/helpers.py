@@ -25,10 +25,13 @@ def snapshot(mp):
     return dict(cen=cen.copy(), q=q.copy(), t=t.copy(), corner=mp.cubes(0), surf=mp.cubes(1))
 
 
-def run_sequence(seed, n_frames, n_az=2000, snapshot_frames=(), keep_features=True):
+def run_sequence(seed, n_frames, n_az=2000, snapshot_frames=(), keep_features=True, line_res=0.4,
+                 plane_res=0.8, voxel_order=0):
     """Oracle pipeline (scan registration -> odometry -> mapping) over a synthetic sequence.
-    For frames in snapshot_frames, the mapper state BEFORE solveMapping is recorded."""
-    sr, od, mp = O.ScanRegistration(), O.LaserOdometry(), O.LaserMapping()
+    For frames in snapshot_frames, the mapper state BEFORE solveMapping is recorded.
+    line_res / plane_res: the mapper's VoxelGrid leaves; voxel_order: the summation order of the
+    mapper's VoxelGrids (0 PCL's, 1 input order) -- scan registration and odometry stay in PCL's."""
+    sr, od, mp = O.ScanRegistration(), O.LaserOdometry(), O.LaserMapping(line_res, plane_res)
     frames = []
     for f in range(n_frames):
         xyz, gt = synth.frame(seed, f, n_az)
@@ -42,8 +45,9 @@ def run_sequence(seed, n_frames, n_az=2000, snapshot_frames=(), keep_features=Tr
             rec.update(corner=corner, surf=surf)
         if f in snapshot_frames:
             rec["before"] = snapshot(mp)
-        mp.input(corner, surf, None, q, t)
-        mp.solve()
+        with O.voxel_order(voxel_order):
+            mp.input(corner, surf, None, q, t)
+            mp.solve()
         rec["pose"] = mp.pose()
         rec["stats"] = mp.stats()
         if f in snapshot_frames:

@@ -60,6 +60,29 @@ def test_bad_arguments_are_rejected():
     assert L.loam_scanreg_destroy(None) in (0, -1)
 
 
+@pytest.mark.parametrize("field", ["mapping_line_resolution", "mapping_plane_resolution"])
+@pytest.mark.parametrize("leaf", [0.0, -0.4, float("nan"), float("inf"), -float("inf"), 1e-60])
+def test_mapper_create_rejects_bad_leaf(field, leaf):
+    """a VoxelGrid leaf that is not finite and positive (as the float the kernels use: 1e-60 is 0)
+    is refused before any device work, with a text; small positive leaves are not"""
+    L = _core.lib()
+    h = ctypes.c_void_p()
+    p = _core.default_params(**{field: leaf})
+    assert L.loam_mapper_create(ctypes.byref(p), 0, 1, ctypes.byref(h)) == -1  # LOAM_ERR_ARG
+    assert not h.value
+    assert field in L.loam_last_error().decode()
+    c = ctypes.c_void_p()  # the sharded entry point creates the same way
+    assert L.loam_comm_create(0, 1, None, ctypes.byref(c)) == 0
+    assert L.loam_mapper_create_sharded(ctypes.byref(p), 0, 1, c, ctypes.byref(h)) == -1
+    assert field in L.loam_last_error().decode() and not h.value
+    assert L.loam_comm_destroy(c) == 0
+    ok = _core.default_params(**{field: 1e-3})
+    rc = L.loam_mapper_create(ctypes.byref(ok), 0, 1, ctypes.byref(h))
+    assert rc != -1 or field not in L.loam_last_error().decode()  # (no device: another error)
+    if rc == 0:
+        L.loam_mapper_destroy(h)
+
+
 @pytest.mark.skipif(gpu_available(), reason="checks the no-device path")
 def test_no_device_fails_loudly():
     from loam_amd.mapping import BatchMapper

@@ -77,9 +77,9 @@ def _run_ranks(size, body, transport="threads"):
     return res
 
 
-def _sequence_body(seq):
+def _sequence_body(seq, **params):
     def body(rank, comm):
-        m = BatchMapper(1, comm=comm)
+        m = BatchMapper(1, comm=comm, **params)
         poses, stats = [], []
         for rec in seq:
             m.input(0, rec["corner"], rec["surf"], rec["q_wodom"], rec["t_wodom"])
@@ -116,7 +116,14 @@ def test_single_rank_comm_matches_unsharded(seq, unsharded):
 def test_ranks_match_unsharded(seq, unsharded, size, transport):
     ref, ref_maps = unsharded
     res = _run_ranks(size, _sequence_body(seq), transport)
-    for f in range(N_FRAMES):
+    _assert_ranks_match_unsharded(res, ref, ref_maps, size, (0.4, 0.8))
+
+
+def _assert_ranks_match_unsharded(res, ref, ref_maps, size, leaf):
+    """res: _sequence_body's result of every rank; ref, ref_maps: the unsharded handle's per-frame
+    (pose, stats) and final maps on the same frames; leaf: (line, plane) resolution of both"""
+    assert all(len(r[0]) == len(ref) and len(r[1]) == len(ref) for r in res)
+    for f in range(len(ref)):
         q0, t0 = res[0][0][f]
         for r in range(1, size):  # identical step on every rank
             q, t = res[r][0][f]
@@ -126,7 +133,6 @@ def test_ranks_match_unsharded(seq, unsharded, size, transport):
         st = res[0][1][f]
         assert st == sr, (f, st, sr)
         assert np.linalg.norm(t0 - tr) < 1e-6 and quat_angle(q0, qr) < 1e-6, f
-    leaf = (0.4, 0.8)
     for which in range(2):
         cubes = set()
         for r in range(size):

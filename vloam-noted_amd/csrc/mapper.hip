@@ -493,6 +493,15 @@ static int32_t mapper_create(const loam_params* p, int32_t device, int32_t n_str
     return LOAM_ERR_ARG;
   }
   *out = nullptr;
+  if (p) {
+    // the VoxelGrid leaves as the kernels see them (float): finite and positive.  Small positive
+    // leaves are PCL's business (its "leaf size is too small" rule, voxel.h)
+    for (const double leaf : {p->mapping_line_resolution, p->mapping_plane_resolution})
+      if (!std::isfinite(leaf) || !(leaf < 3.0e38) || !((float)leaf > 0.f)) {
+        set_error("loam_mapper_create: mapping_line_resolution / mapping_plane_resolution must be finite and > 0");
+        return LOAM_ERR_ARG;
+      }
+  }
   TRY(ensure_device(device));
   LOAM_HIP(hipSetDevice(device));
   vh_spin_limit_from_env(device);

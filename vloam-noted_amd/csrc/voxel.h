@@ -75,7 +75,8 @@ struct VoxSeg {
   // the cube lies within [corner, corner + 50] (laser_mapping.cpp:747-756), so the voxel keys can
   // be taken relative to the corner's voxel instead of the points' bounding box: the same order
   // (PCL's idx is lexicographic in (z, y, x) whatever its origin) without the bounding-box pass;
-  // a point outside the margin (content set through the API) falls back to the full filter
+  // a point outside the margin (content set through the API) falls back to the full filter, and
+  // so does a leaf so small that the key box would pass INT_MAX voxels
   int anchored = 0;
   int anchor[3] = {0, 0, 0};
 };
@@ -870,8 +871,8 @@ __device__ inline void vx_copy_through(const VoxSeg& S, uint32_t* sbase) {
 //   voxels holding only A points       -> (0 + a1 + ...) / n, inserted in voxel order
 // A's voxels go into an LDS hash (with member lists); C points look themselves up in it.  Only
 // the voxels holding A points alone need sorting, and there are few: the map is dense where
-// new points land.  Returns false, with nothing written, when the grid overflows (the caller
-// then runs the full filter).
+// new points land.  Returns false, with nothing written, when the grid overflows or the leaf is too
+// small for anchored keys (the caller then runs the full filter).
 // HOT (PCL's summation order wanted, exact_voxel_order = 1): a voxel of at most 2 members sums
 // alike in any order ((0 + a) + b == (0 + b) + a in IEEE arithmetic: commutative, and the leading
 // 0 + x turns a -0 into +0 either way), so the merge gives PCL's bits for it.  A voxel of 3 or
@@ -912,10 +913,16 @@ __device__ inline bool vx_merge_fixed_point(const VoxSeg& S, uint32_t* lds) {
   int W = 0;  // anchored: voxels per axis of the key box
   if (S.anchored) {  // keys from the cube's corner voxel (VoxSeg::anchored): no bounding-box pass
     g.inv = 1.0f / S.leaf;
+    // the 50 m edge, one voxel of margin on each side, rounding.  A box of more than INT_MAX voxels
+    // (W > 1290: 1290^3 < 2^31 <= 1291^3; leaf below ~0.039 m) has no 32-bit keys, two voxels 2^32
+    // apart would be averaged into one point: no merge then (nothing is written yet, the test is
+    // uniform), and the full filter's bounding-box keys come under PCL's own overflow rule
+    const float wf = ceilf(50.0f * g.inv) + 3.0f;
+    if (!(wf <= 1290.0f)) return false;
+    W = (int)wf;
     g.minbx = (int)floorf((float)S.anchor[0] * g.inv) - 1;
     g.minby = (int)floorf((float)S.anchor[1] * g.inv) - 1;
     g.minbz = (int)floorf((float)S.anchor[2] * g.inv) - 1;
-    W = (int)ceilf(50.0f * g.inv) + 3;  // the 50 m edge, one voxel of margin on each side, rounding
     g.mul1 = W;
     g.mul2 = W * W;
     g.nvox = (unsigned long long)W * W * W;
