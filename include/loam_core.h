@@ -70,6 +70,10 @@ typedef struct loam_params {
 void loam_params_default(loam_params* p);
 const char* loam_last_error(void);
 int32_t loam_version(void);
+/* Host only (works without a device): how many device buffers, page-locked host buffers, streams and
+ * events (out[0..3]) the handles of this process hold right now.  For leak checks: the device-wide
+ * free-memory figure says nothing on a shared GPU. */
+int32_t loam_debug_live_resources(int64_t out[4]);
 
 /* --------------------------------------------------------------------------------------
  * Per-call statistics (the reference's TicToc probes, laser_mapping.cpp:502-811, and the

@@ -46,6 +46,7 @@ def test_header_is_plain_c():
 def test_host_only_entry_points():
     L = _core.lib()
     assert L.loam_version() >= 100
+    assert L.loam_debug_live_resources(ctypes.byref((ctypes.c_int64 * 4)())) == 0
     p = _core.default_params()
     assert p.scan_line == 64 and abs(p.mapping_line_resolution - 0.4) < 1e-12
     assert abs(p.mapping_plane_resolution - 0.8) < 1e-12 and abs(p.minimum_range - 5.0) < 1e-12

@@ -30,6 +30,7 @@ int32_t ensure_device(int32_t device);
     if (rc_ != LOAM_OK) return rc_; \
   } while (0)
 
+#ifdef __HIPCC__  // (host-only programs built without hipcc share the plumbing above)
 // Wave-wide inclusive scan / reductions on 64-lane waves
 __device__ inline int wave_lane() { return threadIdx.x & 63; }
 
@@ -103,5 +104,6 @@ __device__ inline uint32_t wave_incl_scan_u(uint32_t v) {
   }
   return v;
 }
+#endif  // __HIPCC__
 
 }  // namespace loam

@@ -2,13 +2,15 @@
 #include <mutex>
 #include <string>
 
-#include "common.h"
+#include "device_res.h"
 
 namespace loam {
 
 static thread_local std::string g_last_error;
 
 void set_error(const std::string& msg) { g_last_error = msg; }
+
+std::atomic<int64_t> g_live[LIVE_KINDS];
 
 int32_t ensure_device(int32_t device) {
   int n = 0;
@@ -57,5 +59,11 @@ void loam_params_default(loam_params* p) {
 const char* loam_last_error(void) { return loam::g_last_error.c_str(); }
 
 int32_t loam_version(void) { return 100; }
+
+int32_t loam_debug_live_resources(int64_t out[4]) {
+  if (!out) return LOAM_ERR_ARG;
+  for (int k = 0; k < loam::LIVE_KINDS; ++k) out[k] = loam::g_live[k].load();
+  return LOAM_OK;
+}
 
 }  // extern "C"

@@ -23,10 +23,11 @@
 // batched streams fill the chip.
 #include <algorithm>
 #include <cmath>
+#include <memory>
 #include <vector>
 
-#include "common.h"
 #include "depth_dev.h"
+#include "device_res.h"
 
 namespace loam {
 
@@ -268,68 +269,30 @@ __global__ void __launch_bounds__(DP_THREADS) k_dp_query(DepthDev D, const int* 
 using namespace loam;
 
 struct loam_depth {
+  DevStream st;  // first: destroyed after everything below
   int dev = 0;
   int B = 0;
   loam_depth_params P{};
   DepthDev D{};
   std::vector<DepthFrame> hf;
   std::vector<char> processed;  // per stream: buckets of a loam_depth_process are resident
-  std::vector<void*> allocs;
+  DevPool pool;
   float4* stage = nullptr;  // [B][cap] host-input staging
-  int* d_qs = nullptr;      // query stream ids / points / results (grown on demand)
-  float2* d_xy = nullptr;
-  float* d_depth = nullptr;
-  int q_cap = 0;
-  hipStream_t st = nullptr;
-  hipEvent_t ev[2] = {nullptr, nullptr};
+  DevBuf<int> d_qs;         // query stream ids / points / results (grown on demand)
+  DevBuf<float2> d_xy;
+  DevBuf<float> d_depth;
+  DevEvent ev[2];
   float ms = 0.f;
+  ~loam_depth() { (void)hipStreamSynchronize(st); }
 };
 
 namespace {
-
-template <typename T>
-int32_t dp_alloc(loam_depth* h, T** p, size_t n) {
-  void* q = nullptr;
-  const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
-  LOAM_HIP(hipMalloc(&q, bytes));
-  LOAM_HIP(hipMemsetAsync(q, 0, bytes, h->st));
-  h->allocs.push_back(q);
-  *p = reinterpret_cast<T*>(q);
-  return LOAM_OK;
-}
-
-void dp_free(loam_depth* h) {
-  for (void* p : h->allocs) (void)hipFree(p);
-  h->allocs.clear();
-  if (h->d_qs) (void)hipFree(h->d_qs);
-  if (h->d_xy) (void)hipFree(h->d_xy);
-  if (h->d_depth) (void)hipFree(h->d_depth);
-  for (auto& e : h->ev)
-    if (e) (void)hipEventDestroy(e);
-  if (h->st) (void)hipStreamDestroy(h->st);
-}
 
 int32_t dp_check(loam_depth* h, int32_t s) {
   if (!h || s < 0 || s >= h->B) {
     set_error("loam_depth: bad handle or stream");
     return LOAM_ERR_ARG;
   }
-  return LOAM_OK;
-}
-
-int32_t dp_query_cap(loam_depth* h, int n) {
-  if (n <= h->q_cap) return LOAM_OK;
-  if (h->d_qs) (void)hipFree(h->d_qs);
-  if (h->d_xy) (void)hipFree(h->d_xy);
-  if (h->d_depth) (void)hipFree(h->d_depth);
-  h->d_qs = nullptr;
-  h->d_xy = nullptr;
-  h->d_depth = nullptr;
-  h->q_cap = 0;
-  LOAM_HIP(hipMalloc(&h->d_qs, sizeof(int) * n));
-  LOAM_HIP(hipMalloc(&h->d_xy, sizeof(float2) * n));
-  LOAM_HIP(hipMalloc(&h->d_depth, sizeof(float) * n));
-  h->q_cap = n;
   return LOAM_OK;
 }
 
@@ -370,18 +333,12 @@ int32_t loam_depth_create(const loam_depth_params* p, int32_t device, int32_t n_
   *out = nullptr;
   TRY(ensure_device(device));
   LOAM_HIP(hipSetDevice(device));
-  auto* h = new loam_depth;
+  std::unique_ptr<loam_depth> h(new loam_depth);
   h->P = *p;
   h->dev = device;
   h->B = n_streams;
-  auto fail = [&](int32_t r) {
-    dp_free(h);
-    delete h;
-    return r;
-  };
-  if (hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking) != hipSuccess) return fail(LOAM_ERR_HIP);
-  for (auto& e : h->ev)
-    if (hipEventCreate(&e) != hipSuccess) return fail(LOAM_ERR_HIP);
+  TRY(h->st.create());
+  for (auto& e : h->ev) TRY(e.create());
   DepthDev& D = h->D;
   D.B = n_streams;
   D.nchunk = (p->max_points + DP_CHUNK - 1) / DP_CHUNK;
@@ -396,35 +353,31 @@ int32_t loam_depth_create(const loam_depth_params* p, int32_t device, int32_t n_
   }
   for (int k = 0; k < 12; ++k) D.C[k] = p->P_rect0[k];
   const size_t B = n_streams, cap = D.cap, WH = (size_t)D.W * D.H;
-  int32_t rc = LOAM_OK;
-#define DA(ptr, n) \
-  if ((rc = dp_alloc(h, &(ptr), (n))) != LOAM_OK) return fail(rc)
-  DA(D.fr, B);
-  DA(h->stage, B * cap);
-  DA(D.tmp, B * cap);
-  DA(D.chunk_cnt, B * D.nchunk);
-  DA(D.p2d, B * cap);
-  DA(D.bcnt, B * WH);
-  DA(D.bstart, B * (WH + 1));
-  DA(D.bfill, B * WH);
-  DA(D.bslot, B * WH);
-  DA(D.members, B * cap);
-  DA(D.bx, B * WH);
-  DA(D.by, B * WH);
-  DA(D.bd, B * WH);
-  DA(D.dnsp, B * WH);
-#undef DA
+  auto alloc = [&](auto& ptr, size_t n) { return h->pool.alloc(&ptr, n, h->st); };
+  TRY(alloc(D.fr, B));
+  TRY(alloc(h->stage, B * cap));
+  TRY(alloc(D.tmp, B * cap));
+  TRY(alloc(D.chunk_cnt, B * D.nchunk));
+  TRY(alloc(D.p2d, B * cap));
+  TRY(alloc(D.bcnt, B * WH));
+  TRY(alloc(D.bstart, B * (WH + 1)));
+  TRY(alloc(D.bfill, B * WH));
+  TRY(alloc(D.bslot, B * WH));
+  TRY(alloc(D.members, B * cap));
+  TRY(alloc(D.bx, B * WH));
+  TRY(alloc(D.by, B * WH));
+  TRY(alloc(D.bd, B * WH));
+  TRY(alloc(D.dnsp, B * WH));
   h->hf.assign(B, DepthFrame{});
   h->processed.assign(B, 0);
-  if (hipStreamSynchronize(h->st) != hipSuccess) return fail(LOAM_ERR_HIP);
-  *out = h;
+  LOAM_HIP(hipStreamSynchronize(h->st));
+  *out = h.release();
   return LOAM_OK;
 }
 
 int32_t loam_depth_destroy(loam_depth* h) {
   if (!h) return LOAM_ERR_ARG;
   (void)hipSetDevice(h->dev);
-  dp_free(h);
   delete h;
   return LOAM_OK;
 }
@@ -545,7 +498,9 @@ int32_t loam_depth_query(loam_depth* h, int32_t n, const int32_t* streams, const
     }
   if (n == 0) return LOAM_OK;
   LOAM_HIP(hipSetDevice(h->dev));
-  TRY(dp_query_cap(h, n));
+  TRY(h->d_qs.reserve(n));
+  TRY(h->d_xy.reserve(n));
+  TRY(h->d_depth.reserve(n));
   hipStream_t st = h->st;
   LOAM_HIP(hipMemcpyAsync(h->d_qs, streams, sizeof(int) * n, hipMemcpyHostToDevice, st));
   LOAM_HIP(hipMemcpyAsync(h->d_xy, xy, sizeof(float2) * n, hipMemcpyHostToDevice, st));

@@ -41,6 +41,7 @@
 #include <array>
 #include <cstring>
 #include <deque>
+#include <memory>
 #include <vector>
 
 #include "common.h"
@@ -48,6 +49,7 @@
 #include "cellhash.h"
 #include "comm.h"
 #include "cubeindex.h"
+#include "device_res.h"
 #include "lm.h"
 #include "voxel.h"
 #include "voxel_hot.h"
@@ -64,41 +66,6 @@ namespace loam {
 // ---------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------
-// page-locked host array (hipHostMalloc) with the few vector operations used here
-template <typename T>
-struct PinnedArray {
-  T* p = nullptr;
-  size_t n = 0;
-  ~PinnedArray() { release(); }
-  void release() {
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    n = 0;
-  }
-  bool assign(size_t count, const T& v, unsigned flags = hipHostMallocDefault) {
-    release();
-    if (hipHostMalloc(reinterpret_cast<void**>(&p), sizeof(T) * std::max<size_t>(count, 1), flags) != hipSuccess) {
-      p = nullptr;
-      return false;
-    }
-    n = count;
-    for (size_t i = 0; i < n; ++i) p[i] = v;
-    return true;
-  }
-  // mapped and coherent, for the device to read or write in place: its device address (nullptr: failed)
-  T* assign_mapped(size_t count, const T& v) {
-    void* dp = nullptr;
-    if (!assign(count, v, hipHostMallocMapped | hipHostMallocCoherent) ||
-        hipHostGetDevicePointer(&dp, p, 0) != hipSuccess)
-      return nullptr;
-    return static_cast<T*>(dp);
-  }
-  T& operator[](size_t i) { return p[i]; }
-  const T& operator[](size_t i) const { return p[i]; }
-  T* data() { return p; }
-  size_t size() const { return n; }
-};
-
 struct HostStream {
   double q_wmap_wodom[4] = {0, 0, 0, 1}, t_wmap_wodom[3] = {0, 0, 0};
   double q_wodom[4] = {0, 0, 0, 1}, t_wodom[3] = {0, 0, 0};
@@ -190,8 +157,8 @@ struct ParitySlot {
   StreamFrame* hfo_early_dev = nullptr;
   PinnedArray<FrameIn> fin;  // the graph path's frame inputs (k_frame_prep)
   const FrameIn* fin_dev = nullptr;
-  hipEvent_t ev_fr[2] = {nullptr, nullptr};  // frame start / records back (timed)
-  hipEvent_t ev_sin = nullptr;               // the last reads of hsin done
+  DevEvent ev_fr[2];  // frame start / records back (timed)
+  DevEvent ev_sin;    // the last reads of hsin done
   float4* stack_buf[2] = {nullptr, nullptr};  // [map]
   int* stk_n_buf = nullptr;
   int* stk_err_buf = nullptr;
@@ -200,6 +167,8 @@ struct ParitySlot {
 };
 
 struct loam_mapper {
+  DevStream st;   // the streams first: destroyed after everything below
+  DevStream st2;  // stack VoxelGrid, concurrent with the submap / hash build
   // the status of a frame loam_mapper_solve_async finished to make room (LOAM_ERR_CAPACITY /
   // _SYNC), held for the next loam_mapper_wait / loam_mapper_solve (as LOAM_ERR_EARLIER): the
   // solve_async that finished it returns OK, since it did enqueue its own frame
@@ -207,14 +176,12 @@ struct loam_mapper {
   std::string held_msg;
   loam_params P;
   bool prof = false;
-  std::vector<hipEvent_t> ev_pool;
+  std::vector<DevEvent> ev_pool;
   std::vector<int> ev_fam;  // family of each recorded (start, stop) pair
   double fam_ms[NFAM] = {0}, fam_bytes[NFAM] = {0};
   long long fam_launches[NFAM] = {0};
   int dev = 0, B = 1;
-  hipStream_t st = nullptr;
-  hipStream_t st2 = nullptr;  // stack VoxelGrid, concurrent with the submap / hash build
-  hipEvent_t ev_opt_begin = nullptr, ev_opt_end = nullptr;  // around the optimisation block (host path)
+  DevEvent ev_opt_begin, ev_opt_end;  // around the optimisation block (host path)
   MapperDev D{};
   PinnedArray<StreamFrame> hf;  // pinned: the per-frame H2D / D2H of the stream records
   std::vector<HostStream> hs;
@@ -222,7 +189,7 @@ struct loam_mapper {
   int parity = 0;
   uint32_t* tok_tmp = nullptr;  // [B][2][NCUBE] the shifted fixed-point tokens
   uint32_t* d_new_off = nullptr;
-  std::vector<void*> allocs;
+  DevPool pool;
   uint32_t frame_counter = 0;
   int n_cu = 256;  // compute units (grid of the worklist kernels)
   // compact an arena once its tail passes this: one frame writes at most the window content
@@ -231,7 +198,7 @@ struct loam_mapper {
   uint32_t compact_at = 0;
   int lm_G = 0;  // workgroups per stream of k_lm_round (0: two-kernel path k_lm_eval / k_lm_step)
   bool want_ipc = false;            // cross-process ranks: set up the IPC peer buffers at create
-  void* ipc_own = nullptr;          // this rank's LM peer buffer (ipc_peer_setup)
+  DevBuf<char> ipc_own;             // this rank's LM peer buffer (ipc_peer_setup)
   std::vector<void*> ipc_open;      // the other ranks' buffers, mapped from their IPC handles
   int knn_cs = 0;     // k_knn: 8 lanes per query splitting the cells (handles of <= 4 streams), else 0
                       // (one lane per query)
@@ -259,63 +226,28 @@ struct loam_mapper {
   unsigned long long* done_early_dev = nullptr;
   uint32_t grow_max = 0;     // largest arena growth of one frame seen (compaction foresight)
   std::vector<std::array<uint32_t, 2>> last_tail;
-  hipEvent_t ev_stack = nullptr;   // after the last stack launch (on st2)
+  DevEvent ev_stack;               // after the last stack launch (on st2)
   // publish-side buffers (grown on demand)
   uint32_t* d_map_off = nullptr;  // [2 * NCUBE + 1]
-  float4* d_pub = nullptr;
-  size_t pub_cap = 0;
+  DevBuf<float4> d_pub;
+  // what is not a plain resource goes here; the members release themselves after it
+  ~loam_mapper() {
+    (void)hipStreamSynchronize(st);
+    (void)hipStreamSynchronize(st2);
+    if (D.lm_peer && comm) comm_peer_release(comm);  // the group's LM peer buffer
+    for (void* p : ipc_open) (void)hipIpcCloseMemHandle(p);
+    for (auto& gp : gexec)
+      for (auto& g : gp)
+        if (g) (void)hipGraphExecDestroy(g);
+  }
 };
 
 namespace {
-
-template <typename T>
-int32_t dalloc(loam_mapper* h, T** p, size_t count) {
-  void* q = nullptr;
-  size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-  LOAM_HIP(hipMalloc(&q, bytes));
-  // zero on the handle's own (non-blocking) stream: a null-stream memset is not ordered
-  // before this stream's kernels; create() synchronizes the stream before returning
-  LOAM_HIP(hipMemsetAsync(q, 0, bytes, h->st));
-  h->allocs.push_back(q);
-  *p = reinterpret_cast<T*>(q);
-  return LOAM_OK;
-}
 
 uint32_t next_pow2(uint32_t v) {
   uint32_t p = 1;
   while (p < v) p <<= 1;
   return p;
-}
-
-void free_all(loam_mapper* h) {
-  if (h->D.lm_peer && h->comm) {  // the group's LM peer buffer (kernels done: the caller synchronized)
-    comm_peer_release(h->comm);
-    h->D.lm_peer = nullptr;
-    h->D.lm_peer_flag = nullptr;
-  }
-  for (void* p : h->ipc_open) (void)hipIpcCloseMemHandle(p);
-  h->ipc_open.clear();
-  if (h->ipc_own) (void)hipFree(h->ipc_own);
-  h->ipc_own = nullptr;
-  h->D.ipc_tab = nullptr;
-  for (void* p : h->allocs) (void)hipFree(p);
-  h->allocs.clear();
-  if (h->d_pub) (void)hipFree(h->d_pub);
-  h->d_pub = nullptr;
-  h->pub_cap = 0;
-  for (auto& gp : h->gexec)
-    for (auto& g : gp)
-      if (g) (void)hipGraphExecDestroy(g);
-  for (auto& e : h->ev_pool) (void)hipEventDestroy(e);
-  if (h->ev_stack) (void)hipEventDestroy(h->ev_stack);
-  for (ParitySlot& S : h->slot)
-    for (hipEvent_t e : {S.ev_sin, S.ev_fr[0], S.ev_fr[1]})
-      if (e) (void)hipEventDestroy(e);
-  h->ev_pool.clear();
-  if (h->ev_opt_begin) (void)hipEventDestroy(h->ev_opt_begin);
-  if (h->ev_opt_end) (void)hipEventDestroy(h->ev_opt_end);
-  if (h->st) (void)hipStreamDestroy(h->st);
-  if (h->st2) (void)hipStreamDestroy(h->st2);
 }
 
 void host_initial_guess(HostStream& H, double* pose) {
@@ -404,6 +336,7 @@ static int32_t ipc_peer_setup(loam_mapper* h) {
   static_assert(sizeof(Msg) % 8 == 0, "exchange record");
   Msg mine{};
   void* buf = nullptr;
+  DevBuf<char> own;
   // uncached device memory where the runtime offers it (its accesses bypass the caches of every
   // agent, as RCCL's flags); else ordinary device memory (the accesses are system-scope atomics)
   if (hipExtMallocWithFlags(&buf, bytes, hipDeviceMallocUncached) != hipSuccess) {
@@ -414,22 +347,14 @@ static int32_t ipc_peer_setup(loam_mapper* h) {
       buf = nullptr;
     }
   }
+  own.adopt(static_cast<char*>(buf), bytes);
   mine.ok = buf && hipMemset(buf, 0, bytes) == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
             hipIpcGetMemHandle(&mine.hdl, buf) == hipSuccess;
   if (!mine.ok) (void)hipGetLastError();
-  Msg* dsend = nullptr;
-  Msg* drecv = nullptr;
+  DevBuf<Msg> dsend, drecv;
   std::vector<Msg> all(R);
-  auto cleanup = [&] {
-    if (dsend) (void)hipFree(dsend);
-    if (drecv) (void)hipFree(drecv);
-    dsend = drecv = nullptr;
-  };
-  LOAM_HIP(hipMalloc(&dsend, sizeof(Msg)));
-  if (hipMalloc(&drecv, sizeof(Msg) * R) != hipSuccess) {
-    cleanup();
-    return LOAM_ERR_HIP;
-  }
+  TRY(dsend.reserve(1));
+  TRY(drecv.reserve(R));
   auto exchange = [&]() -> int32_t {  // mine -> all (every rank's, in rank order)
     if (hipMemcpy(dsend, &mine, sizeof(Msg), hipMemcpyHostToDevice) != hipSuccess) return LOAM_ERR_HIP;
     TRY(comm_allgather(c, dsend, drecv, (int64_t)sizeof(Msg), h->st));
@@ -466,18 +391,17 @@ static int32_t ipc_peer_setup(loam_mapper* h) {
     ok = rc == LOAM_OK;
     for (int r = 0; r < R && ok; ++r) ok = all[r].ok != 0;
   }
-  cleanup();
-  if (!ok) {  // every rank arrives here alike: the two-kernel path
+  dsend.release();
+  drecv.release();
+  if (!ok) {  // every rank arrives here alike: the two-kernel path (own frees the buffer)
     for (void* p : h->ipc_open) (void)hipIpcCloseMemHandle(p);
     h->ipc_open.clear();
-    if (buf) (void)hipFree(buf);
     return rc;
   }
-  h->ipc_own = buf;
+  h->ipc_own = std::move(own);
   unsigned long long* dtab = nullptr;
-  const int32_t arc = dalloc(h, &dtab, tab.size());
-  if (arc != LOAM_OK) return arc;
-  // on the handle's stream, behind dalloc's zero fill there (a null-stream copy is not ordered
+  TRY(h->pool.alloc(&dtab, tab.size(), h->st));
+  // on the handle's stream, behind the pool's zero fill there (a null-stream copy is not ordered
   // after it: the fill could land last and leave null peer pointers)
   LOAM_HIP(hipMemcpyAsync(dtab, tab.data(), sizeof(unsigned long long) * tab.size(), hipMemcpyHostToDevice, h->st));
   LOAM_HIP(hipStreamSynchronize(h->st));
@@ -506,7 +430,8 @@ static int32_t mapper_create(const loam_params* p, int32_t device, int32_t n_str
   LOAM_HIP(hipSetDevice(device));
   vh_spin_limit_from_env(device);
   lm_peer_spin_limit_from_env(device);
-  auto* h = new loam_mapper;
+  std::unique_ptr<loam_mapper> hold(new loam_mapper);
+  loam_mapper* const h = hold.get();
   if (p) h->P = *p; else loam_params_default(&h->P);
   h->dev = device;
   h->B = n_streams;
@@ -592,23 +517,17 @@ static int32_t mapper_create(const loam_params* p, int32_t device, int32_t n_str
   D.leaf[0] = (float)h->P.mapping_line_resolution;
   D.leaf[1] = (float)h->P.mapping_plane_resolution;
   const size_t B = n_streams;
-  auto fail = [&](int32_t rc) {
-    free_all(h);
-    delete h;
-    return rc;
-  };
-  int32_t rc = LOAM_OK;
-#define ALLOC(ptr, n) \
-  if ((rc = dalloc(h, &(ptr), (n))) != LOAM_OK) return fail(rc)
-  if (hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking) != hipSuccess) return fail(LOAM_ERR_HIP);
-  if (hipStreamCreateWithFlags(&h->st2, hipStreamNonBlocking) != hipSuccess) return fail(LOAM_ERR_HIP);
-  if (hipEventCreate(&h->ev_opt_begin) != hipSuccess || hipEventCreate(&h->ev_opt_end) != hipSuccess ||
-      hipEventCreateWithFlags(&h->ev_stack, hipEventDisableTiming) != hipSuccess)
-    return fail(LOAM_ERR_HIP);
-  for (ParitySlot& S : h->slot)
-    if (hipEventCreateWithFlags(&S.ev_sin, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreate(&S.ev_fr[0]) != hipSuccess || hipEventCreate(&S.ev_fr[1]) != hipSuccess)
-      return fail(LOAM_ERR_HIP);
+  auto alloc = [&](auto& ptr, size_t n) { return h->pool.alloc(&ptr, n, h->st); };
+  TRY(h->st.create());
+  TRY(h->st2.create());
+  TRY(h->ev_opt_begin.create());
+  TRY(h->ev_opt_end.create());
+  TRY(h->ev_stack.create(hipEventDisableTiming));
+  for (ParitySlot& S : h->slot) {
+    TRY(S.ev_sin.create(hipEventDisableTiming));
+    TRY(S.ev_fr[0].create());
+    TRY(S.ev_fr[1].create());
+  }
   {
     const char* denv = std::getenv("LOAM_DEFER_EVERY");  // tests: force the deferral path
     D.defer_every = denv ? std::max(0, std::atoi(denv)) : 0;
@@ -623,120 +542,118 @@ static int32_t mapper_create(const loam_params* p, int32_t device, int32_t n_str
   D.knn_blk = n_streams <= 4 ? 4 * CORR_BLK : CORR_BLK;
   if (const char* benv = std::getenv("LOAM_KNN_BLK"))  // measurement override (cell-split workgroups per stream)
     if (h->knn_cs) D.knn_blk = std::max(1, std::min(64 * CORR_BLK, std::atoi(benv)));
-  ALLOC(D.fr, B);
+  TRY(alloc(D.fr, B));
   for (int m = 0; m < 2; ++m) {
-    ALLOC(D.in_pts[m], B * D.max_in);
-    for (ParitySlot& S : h->slot) ALLOC(S.stack_buf[m], B * D.max_in);
+    TRY(alloc(D.in_pts[m], B * D.max_in));
+    for (ParitySlot& S : h->slot) TRY(alloc(S.stack_buf[m], B * D.max_in));
   }
-  ALLOC(D.arena, B * 2 * 2 * (size_t)D.map_cap);
-  ALLOC(D.carena, B * 2 * 2 * (size_t)D.map_cap);
-  ALLOC(D.ctab, B * 2 * 2 * 4 * (size_t)D.map_cap);
-  ALLOC(h->cube_tab[0], B * 2 * NCUBE);
-  ALLOC(h->cube_tab[1], B * 2 * NCUBE);
-  ALLOC(D.extra_flag, B * 2 * NCUBE);
+  TRY(alloc(D.arena, B * 2 * 2 * (size_t)D.map_cap));
+  TRY(alloc(D.carena, B * 2 * 2 * (size_t)D.map_cap));
+  TRY(alloc(D.ctab, B * 2 * 2 * 4 * (size_t)D.map_cap));
+  TRY(alloc(h->cube_tab[0], B * 2 * NCUBE));
+  TRY(alloc(h->cube_tab[1], B * 2 * NCUBE));
+  TRY(alloc(D.extra_flag, B * 2 * NCUBE));
   D.knn_stride = B * 2 * (size_t)D.max_in;
-  ALLOC(D.knn_id, 5 * D.knn_stride);
-  ALLOC(D.r_type, B * 2 * (size_t)D.max_in);
-  ALLOC(D.r_px, B * 2 * (size_t)D.max_in);
-  ALLOC(D.r_py, B * 2 * (size_t)D.max_in);
-  ALLOC(D.r_pz, B * 2 * (size_t)D.max_in);
+  TRY(alloc(D.knn_id, 5 * D.knn_stride));
+  TRY(alloc(D.r_type, B * 2 * (size_t)D.max_in));
+  TRY(alloc(D.r_px, B * 2 * (size_t)D.max_in));
+  TRY(alloc(D.r_py, B * 2 * (size_t)D.max_in));
+  TRY(alloc(D.r_pz, B * 2 * (size_t)D.max_in));
   for (int k = 0; k < 3; ++k) {
-    ALLOC(D.r_a[k], B * 2 * (size_t)D.max_in);
-    ALLOC(D.r_b[k], B * 2 * (size_t)D.max_in);
+    TRY(alloc(D.r_a[k], B * 2 * (size_t)D.max_in));
+    TRY(alloc(D.r_b[k], B * 2 * (size_t)D.max_in));
   }
-  ALLOC(D.ins_pts, B * 2 * (size_t)D.max_in);
-  ALLOC(D.ins_tag, B * 2 * (size_t)D.max_in);
-  ALLOC(D.ins_sorted, B * 2 * (size_t)D.max_in);
-  ALLOC(D.ins_off, B * 2 * (size_t)(INS_SLOTS + 1));
-  ALLOC(D.stable_tok, B * 2 * (size_t)NCUBE);
-  ALLOC(h->tok_tmp, B * 2 * (size_t)NCUBE);
-  ALLOC(D.dbg, LOAM_DEBUG_COUNTERS);
+  TRY(alloc(D.ins_pts, B * 2 * (size_t)D.max_in));
+  TRY(alloc(D.ins_tag, B * 2 * (size_t)D.max_in));
+  TRY(alloc(D.ins_sorted, B * 2 * (size_t)D.max_in));
+  TRY(alloc(D.ins_off, B * 2 * (size_t)(INS_SLOTS + 1)));
+  TRY(alloc(D.stable_tok, B * 2 * (size_t)NCUBE));
+  TRY(alloc(h->tok_tmp, B * 2 * (size_t)NCUBE));
+  TRY(alloc(D.dbg, LOAM_DEBUG_COUNTERS));
   {  // phase cycle counters (readcyclecounter + device-scope atomics in the kernels): diagnostics only
     const char* penv = std::getenv("LOAM_PHASE_COUNTERS");
     D.pdbg = (penv && std::atoi(penv) > 0) ? D.dbg : nullptr;
   }
-  ALLOC(D.vx_pts, B * 2 * (size_t)D.scratch_cap);
+  TRY(alloc(D.vx_pts, B * 2 * (size_t)D.scratch_cap));
   if (D.pcl_order) {
     const size_t ps = mp_scratch(D);
-    ALLOC(D.pe, B * 2 * ps);
-    ALLOC(D.pa, B * 2 * ps);
-    ALLOC(D.pb, B * 2 * ps);
-    ALLOC(D.ps, B * 2 * ps);
-    ALLOC(D.pseg, B * 2 * (mp_pseg(ps) + 9));
+    TRY(alloc(D.pe, B * 2 * ps));
+    TRY(alloc(D.pa, B * 2 * ps));
+    TRY(alloc(D.pb, B * 2 * ps));
+    TRY(alloc(D.ps, B * 2 * ps));
+    TRY(alloc(D.pseg, B * 2 * (mp_pseg(ps) + 9)));
   }
-  ALLOC(D.vx_idx, B * 2 * (size_t)D.scratch_cap);
-  ALLOC(D.stk_part, B * 2 * (size_t)STACK_K_MAX);
+  TRY(alloc(D.vx_idx, B * 2 * (size_t)D.scratch_cap));
+  TRY(alloc(D.stk_part, B * 2 * (size_t)STACK_K_MAX));
   for (ParitySlot& S : h->slot) {
-    ALLOC(S.stk_n_buf, B * 2);
-    ALLOC(S.stk_err_buf, B);
+    TRY(alloc(S.stk_n_buf, B * 2));
+    TRY(alloc(S.stk_err_buf, B));
     // few streams: the stack inputs in page-locked host memory the stack kernels read in place
     // (mapped), no H2D copy ahead of the stack VoxelGrid, which heads the blocking frame's critical
     // path; many streams: a device copy (256 workgroups reading host memory cost the stack family
     // ~0.05 ms per step at B = 128, profiles/r6_member_chunks_ab.txt)
     if (B <= 4) {
-      if (!(S.sin_buf = S.hsin.assign_mapped(B, StackIn{}))) return fail(LOAM_ERR_HIP);
+      TRY(S.hsin.assign_mapped(B, StackIn{}, &S.sin_buf));
     } else {
-      ALLOC(S.sin_buf, B);
-      if (!S.hsin.assign(B, StackIn{})) return fail(LOAM_ERR_HIP);
+      TRY(alloc(S.sin_buf, B));
+      TRY(S.hsin.assign(B, StackIn{}));
     }
   }
   bind_stack_parity(h, D, 0);
-  ALLOC(h->d_stk_ready, 2);
-  ALLOC(D.stk_pts, B * 2 * (size_t)D.max_in);
-  ALLOC(D.stk_idx, B * 2 * (size_t)D.max_in);
-  ALLOC(D.partials, B * (size_t)D.max_chunks * LM_NACC);
-  ALLOC(D.lm_sync, B * 2 * LM_SYNC_WORDS);
-  ALLOC(D.lm_xpub, B * 2 * 8);
-  ALLOC(D.tickets, B);
-  ALLOC(D.lm_tick, B);
+  TRY(alloc(h->d_stk_ready, 2));
+  TRY(alloc(D.stk_pts, B * 2 * (size_t)D.max_in));
+  TRY(alloc(D.stk_idx, B * 2 * (size_t)D.max_in));
+  TRY(alloc(D.partials, B * (size_t)D.max_chunks * LM_NACC));
+  TRY(alloc(D.lm_sync, B * 2 * LM_SYNC_WORDS));
+  TRY(alloc(D.lm_xpub, B * 2 * 8));
+  TRY(alloc(D.tickets, B));
+  TRY(alloc(D.lm_tick, B));
   D.rq_cap = B * 2 * INS_SLOTS;
-  ALLOC(D.rq, (size_t)RQ_CLASSES * D.rq_cap);
-  ALLOC(D.rq_ctl, RQ_CLASSES);
-  ALLOC(h->d_map_off, 2 * NCUBE + 1);
-  ALLOC(h->d_new_off, B * 2 * (NCUBE + 1));
+  TRY(alloc(D.rq, (size_t)RQ_CLASSES * D.rq_cap));
+  TRY(alloc(D.rq_ctl, RQ_CLASSES));
+  TRY(alloc(h->d_map_off, 2 * NCUBE + 1));
+  TRY(alloc(h->d_new_off, B * 2 * (NCUBE + 1)));
   if (D.sharded) {
     for (int m = 0; m < 2; ++m) D.blk_v[m] = shard_block_voxels(D.leaf[m]);
     const size_t nq = B * 2 * (size_t)D.max_in;
     NnRec* recv = nullptr;
-    ALLOC(D.wcnt, B * 2 * (size_t)WIN_MAX);
-    ALLOC(D.nn_send, nq);
+    TRY(alloc(D.wcnt, B * 2 * (size_t)WIN_MAX));
+    TRY(alloc(D.nn_send, nq));
     if (D.nrank > 1) {
-      ALLOC(recv, nq * D.nrank);
+      TRY(alloc(recv, nq * D.nrank));
       D.nn_recv = recv;
     } else {
       D.nn_recv = D.nn_send;  // one rank: the all-gather is the identity
     }
-    ALLOC(D.nn_xyz, 5 * nq);
-    ALLOC(D.lm_red, B * (size_t)LM_NACC);
-    ALLOC(D.pose_x, (size_t)D.nrank * B * 8);
-    ALLOC(h->d_q_off, B + 1);
+    TRY(alloc(D.nn_xyz, 5 * nq));
+    TRY(alloc(D.lm_red, B * (size_t)LM_NACC));
+    TRY(alloc(D.pose_x, (size_t)D.nrank * B * 8));
+    TRY(alloc(h->d_q_off, B + 1));
     D.q_off = h->d_q_off;
-    if (!h->q_off.assign(2 * (B + 1), 0)) return fail(LOAM_ERR_HIP);  // [parity][B + 1]
+    TRY(h->q_off.assign(2 * (B + 1), 0));  // [parity][B + 1]
     if (D.nrank == 1) {  // fixed query slots: no per-frame host read of the stack sizes
       for (size_t s = 0; s <= B; ++s) h->q_off[s] = (int)(s * 2 * (size_t)D.max_in);
-      if (hipMemcpyAsync(h->d_q_off, h->q_off.data(), sizeof(int) * (B + 1), hipMemcpyHostToDevice, h->st) !=
-          hipSuccess)
-        return fail(LOAM_ERR_HIP);
+      LOAM_HIP(hipMemcpyAsync(h->d_q_off, h->q_off.data(), sizeof(int) * (B + 1), hipMemcpyHostToDevice, h->st));
     }
   }
-#undef ALLOC
   D.cube_tab = h->cube_tab[0];
-  if (!h->hf.assign(B, StreamFrame{})) return fail(LOAM_ERR_HIP);
-  for (ParitySlot& S : h->slot)
-    if (!(S.hfo_dev = S.hfo.assign_mapped(B, StreamFrame{})) || !(S.fin_dev = S.fin.assign_mapped(B, FrameIn{})) ||
-        !(S.hfo_early_dev = S.hfo_early.assign_mapped(B, StreamFrame{})))
-      return fail(LOAM_ERR_HIP);
-  if (!(h->done_dev = h->done.assign_mapped(2, 0ull)) || !(h->done_early_dev = h->done_early.assign_mapped(2, 0ull)))
-    return fail(LOAM_ERR_HIP);
+  TRY(h->hf.assign(B, StreamFrame{}));
+  for (ParitySlot& S : h->slot) {
+    TRY(S.hfo.assign_mapped(B, StreamFrame{}, &S.hfo_dev));
+    TRY(S.fin.assign_mapped(B, FrameIn{}, &S.fin_dev));
+    TRY(S.hfo_early.assign_mapped(B, StreamFrame{}, &S.hfo_early_dev));
+  }
+  TRY(h->done.assign_mapped(2, 0ull, &h->done_dev));
+  TRY(h->done_early.assign_mapped(2, 0ull, &h->done_early_dev));
   h->hs.assign(B, HostStream{});
   h->last_tail.assign(B, std::array<uint32_t, 2>{0u, 0u});
   for (size_t s = 0; s < B; ++s) h->hf[s] = fresh_record();
-  if (hipStreamSynchronize(h->st) != hipSuccess) return fail(LOAM_ERR_HIP);  // zero-fills done
+  LOAM_HIP(hipStreamSynchronize(h->st));  // zero-fills done
   if (h->want_ipc) {  // collective: every rank of the comm creates its mapper
-    if ((rc = ipc_peer_setup(h)) != LOAM_OK) return fail(rc);
+    TRY(ipc_peer_setup(h));
     if (!D.ipc_tab) h->lm_G = 0;  // some rank could not map the buffers: the two-kernel path
   }
-  *out = h;
+  *out = hold.release();
   return LOAM_OK;
 }
 
@@ -783,9 +700,6 @@ int32_t loam_mapper_destroy(loam_mapper* h) {
   if (!h) return LOAM_ERR_ARG;
   (void)hipSetDevice(h->dev);
   while (!h->q.empty()) (void)finish_oldest(h);
-  (void)hipStreamSynchronize(h->st);
-  (void)hipStreamSynchronize(h->st2);
-  free_all(h);
   delete h;
   return LOAM_OK;
 }
@@ -871,19 +785,19 @@ int32_t loam_mapper_input_device(loam_mapper* h, int32_t s, const float* corner,
 }
 
 // HIP events around each launch when profiling is on (accumulated per kernel family)
-static hipError_t prof_begin(loam_mapper* h, int fam, hipEvent_t* stop, hipStream_t st) {
+static int32_t prof_begin(loam_mapper* h, int fam, hipEvent_t* stop, hipStream_t st) {
   *stop = nullptr;
-  if (!h->prof) return hipSuccess;
+  if (!h->prof) return LOAM_OK;
   size_t k = h->ev_fam.size() * 2;
   while (h->ev_pool.size() < k + 2) {
-    hipEvent_t e;
-    hipError_t err = hipEventCreate(&e);
-    if (err != hipSuccess) return err;
-    h->ev_pool.push_back(e);
+    DevEvent e;
+    TRY(e.create());
+    h->ev_pool.push_back(std::move(e));
   }
   h->ev_fam.push_back(fam);
   *stop = h->ev_pool[k + 1];
-  return hipEventRecord(h->ev_pool[k], st);
+  LOAM_HIP(hipEventRecord(h->ev_pool[k], st));
+  return LOAM_OK;
 }
 // the stop event of a timed launch: recorded by end(), or, when the launch body returns early (a
 // TRY inside it), by the destructor, so no listed (start, stop) pair is left without its stop
@@ -901,7 +815,7 @@ struct ProfStop {
   do {                                                  \
     ProfStop stop_;                                     \
     stop_.st = (stream);                                \
-    LOAM_HIP(prof_begin(h, (fam), &stop_.ev, (stream))); \
+    TRY(prof_begin(h, (fam), &stop_.ev, (stream)));      \
     __VA_ARGS__;                                        \
     LOAM_HIP(stop_.end());                              \
   } while (0)
@@ -1813,16 +1727,6 @@ int32_t loam_mapper_cube_set(loam_mapper* h, int32_t s, int32_t which, int32_t c
   return build_cube_index(h, s, which, cube, cube + 1);
 }
 
-static int32_t pub_reserve(loam_mapper* h, size_t n) {
-  if (n <= h->pub_cap) return LOAM_OK;
-  if (h->d_pub) (void)hipFree(h->d_pub);
-  h->d_pub = nullptr;
-  h->pub_cap = 0;
-  LOAM_HIP(hipMalloc(&h->d_pub, sizeof(float4) * std::max<size_t>(n, 1)));
-  h->pub_cap = n;
-  return LOAM_OK;
-}
-
 int32_t loam_mapper_map_copy(loam_mapper* h, int32_t s, float* out, int64_t cap) {
   SETTLE(h);
   TRY(check_stream(h, s));
@@ -1838,7 +1742,7 @@ int32_t loam_mapper_map_copy(loam_mapper* h, int32_t s, float* out, int64_t cap)
   LOAM_HIP(hipStreamSynchronize(h->st));
   if ((int64_t)total > cap) return (int32_t)total;  // the count only
   if (total) {
-    TRY(pub_reserve(h, total));
+    TRY(h->d_pub.reserve(total));
     k_map_gather<<<512, 256, 0, h->st>>>(D, s, h->d_map_off, h->d_pub);
     LOAM_HIP(hipGetLastError());
     LOAM_HIP(hipMemcpyAsync(out, h->d_pub, sizeof(float4) * total, hipMemcpyDeviceToHost, h->st));
@@ -1857,7 +1761,7 @@ static int32_t register_common(loam_mapper* h, int32_t s, const float* in, int32
   const float4* src = reinterpret_cast<const float4*>(in);
   float4* dst = reinterpret_cast<float4*>(out);
   if (!device) {
-    TRY(pub_reserve(h, n));
+    TRY(h->d_pub.reserve(n));
     LOAM_HIP(hipMemcpyAsync(h->d_pub, in, sizeof(float4) * n, hipMemcpyHostToDevice, h->st));
     src = dst = h->d_pub;
   }

@@ -27,10 +27,12 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <vector>
 
 #include "common.h"
 #include "device_math.h"
+#include "device_res.h"
 #include "lm.h"
 
 namespace loam {
@@ -492,42 +494,21 @@ struct OdomHost {
 using namespace loam;
 
 struct loam_odometry {
+  DevStream st;  // first: destroyed after everything below
   int dev = 0;
   int B = 0;
   int G = 1;
   loam_params P{};
   OdomDev D{};
   std::vector<OdomFrame> hf;
-  OdomFrame* hf_pin = nullptr;  // page-locked staging of hf: the per-solve copies stay DMA copies
+  PinnedArray<OdomFrame> hf_pin;  // page-locked staging of hf: the per-solve copies stay DMA copies
   std::vector<OdomHost> hs;
-  std::vector<void*> allocs;
-  hipStream_t st = nullptr;
-  hipEvent_t ev[2] = {nullptr, nullptr};
+  DevPool pool;
+  DevEvent ev[2];
+  ~loam_odometry() { (void)hipStreamSynchronize(st); }
 };
 
 namespace {
-
-template <typename T>
-int32_t od_alloc(loam_odometry* h, T** p, size_t n) {
-  void* q = nullptr;
-  const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
-  LOAM_HIP(hipMalloc(&q, bytes));
-  LOAM_HIP(hipMemsetAsync(q, 0, bytes, h->st));  // on the handle's stream (ordered)
-  h->allocs.push_back(q);
-  *p = reinterpret_cast<T*>(q);
-  return LOAM_OK;
-}
-
-void od_free(loam_odometry* h) {
-  if (h->st) (void)hipStreamSynchronize(h->st);
-  if (h->hf_pin) (void)hipHostFree(h->hf_pin);
-  h->hf_pin = nullptr;
-  for (void* p : h->allocs) (void)hipFree(p);
-  h->allocs.clear();
-  for (auto& e : h->ev)
-    if (e) (void)hipEventDestroy(e);
-  if (h->st) (void)hipStreamDestroy(h->st);
-}
 
 int32_t od_check(loam_odometry* h, int32_t s) {
   if (!h || s < 0 || s >= h->B) {
@@ -547,50 +528,41 @@ int32_t loam_odometry_create(const loam_params* p, int32_t device, int32_t n_str
     return LOAM_ERR_ARG;
   }
   *out = nullptr;
-  int32_t rc = ensure_device(device);
-  if (rc != LOAM_OK) return rc;
+  TRY(ensure_device(device));
   LOAM_HIP(hipSetDevice(device));
-  auto* h = new loam_odometry;
+  std::unique_ptr<loam_odometry> h(new loam_odometry);
   if (p) h->P = *p; else loam_params_default(&h->P);
   if (h->P.mapping_skip_frame < 1) h->P.mapping_skip_frame = 1;
   h->dev = device;
   h->B = n_streams;
-  auto fail = [&](int32_t r) {
-    od_free(h);
-    delete h;
-    return r;
-  };
-  if (hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking) != hipSuccess) return fail(LOAM_ERR_HIP);
-  for (auto& e : h->ev)
-    if (hipEventCreate(&e) != hipSuccess) return fail(LOAM_ERR_HIP);
+  TRY(h->st.create());
+  for (auto& e : h->ev) TRY(e.create());
   OdomDev& D = h->D;
   D.B = n_streams;
   D.cap = std::min(h->P.max_input_points, 65535);  // 16-bit ranks in the build
   const size_t B = n_streams, cap = D.cap;
-#define OA(ptr, n) \
-  if ((rc = od_alloc(h, &(ptr), (n))) != LOAM_OK) return fail(rc)
-  OA(D.fr, B);
-  for (int k = 0; k < 4; ++k) OA(D.stage[k], B * cap);
+  auto alloc = [&](auto& ptr, size_t n) { return h->pool.alloc(&ptr, n, h->st); };
+  TRY(alloc(D.fr, B));
+  for (int k = 0; k < 4; ++k) TRY(alloc(D.stage[k], B * cap));
   for (int c = 0; c < 2; ++c) {
-    OA(D.last[c], B * cap);
-    OA(D.lsort[c], B * cap);
-    OA(D.lsidx[c], B * cap);
-    OA(D.ltab[c], B * (size_t)OD_TAB);
+    TRY(alloc(D.last[c], B * cap));
+    TRY(alloc(D.lsort[c], B * cap));
+    TRY(alloc(D.lsidx[c], B * cap));
+    TRY(alloc(D.ltab[c], B * (size_t)OD_TAB));
   }
-  OA(D.scratch, B * 2 * cap);
-  OA(D.r_type, B * (size_t)OD_MAXQ);
-  OA(D.r_px, B * (size_t)OD_MAXQ);
-  OA(D.r_py, B * (size_t)OD_MAXQ);
-  OA(D.r_pz, B * (size_t)OD_MAXQ);
+  TRY(alloc(D.scratch, B * 2 * cap));
+  TRY(alloc(D.r_type, B * (size_t)OD_MAXQ));
+  TRY(alloc(D.r_px, B * (size_t)OD_MAXQ));
+  TRY(alloc(D.r_py, B * (size_t)OD_MAXQ));
+  TRY(alloc(D.r_pz, B * (size_t)OD_MAXQ));
   for (int k = 0; k < 3; ++k) {
-    OA(D.r_a[k], B * (size_t)OD_MAXQ);
-    OA(D.r_b[k], B * (size_t)OD_MAXQ);
+    TRY(alloc(D.r_a[k], B * (size_t)OD_MAXQ));
+    TRY(alloc(D.r_b[k], B * (size_t)OD_MAXQ));
   }
-  OA(D.partials, B * (size_t)OD_PBLK * LM_NACC);
-  OA(D.corr_part, B * 2 * (size_t)OD_QBLK_MAX * 2);
-  OA(D.lm_sync, B * 2 * LM_SYNC_WORDS);
-  OA(D.lm_xpub, B * 2 * 8);
-#undef OA
+  TRY(alloc(D.partials, B * (size_t)OD_PBLK * LM_NACC));
+  TRY(alloc(D.corr_part, B * 2 * (size_t)OD_QBLK_MAX * 2));
+  TRY(alloc(D.lm_sync, B * 2 * LM_SYNC_WORDS));
+  TRY(alloc(D.lm_xpub, B * 2 * 8));
   {  // workgroups per stream of the LM round (lm.h: shares are claimed by whichever workgroups
      // run, so residency is a speed matter only): one block per CU (256 VGPRs) when they fit
     int occ = 0, cus = 0;
@@ -602,17 +574,15 @@ int32_t loam_odometry_create(const loam_params* p, int32_t device, int32_t n_str
   h->hf.assign(B, OdomFrame{});
   h->hs.assign(B, OdomHost{});
   for (auto& F : h->hf) F.x[3] = 1.0;
-  if (hipHostMalloc(reinterpret_cast<void**>(&h->hf_pin), sizeof(OdomFrame) * B, hipHostMallocDefault) != hipSuccess)
-    return fail(LOAM_ERR_HIP);
-  if (hipStreamSynchronize(h->st) != hipSuccess) return fail(LOAM_ERR_HIP);
-  *out = h;
+  TRY(h->hf_pin.assign(B, OdomFrame{}));
+  LOAM_HIP(hipStreamSynchronize(h->st));
+  *out = h.release();
   return LOAM_OK;
 }
 
 int32_t loam_odometry_destroy(loam_odometry* h) {
   if (!h) return LOAM_ERR_ARG;
   (void)hipSetDevice(h->dev);
-  od_free(h);
   delete h;
   return LOAM_OK;
 }
@@ -705,9 +675,9 @@ int32_t loam_odometry_solve(loam_odometry* h) {
   if (!any) return LOAM_OK;
   hipStream_t st = h->st;
   OdomDev& D = h->D;
-  std::memcpy(h->hf_pin, h->hf.data(), sizeof(OdomFrame) * B);  // the stream is idle (synchronized below)
+  std::memcpy(h->hf_pin.data(), h->hf.data(), sizeof(OdomFrame) * B);  // the stream is idle (synchronized below)
   LOAM_HIP(hipEventRecord(h->ev[0], st));
-  LOAM_HIP(hipMemcpyAsync(D.fr, h->hf_pin, sizeof(OdomFrame) * B, hipMemcpyHostToDevice, st));
+  LOAM_HIP(hipMemcpyAsync(D.fr, h->hf_pin.data(), sizeof(OdomFrame) * B, hipMemcpyHostToDevice, st));
   if (any_inited) {
     // one wave per query: enough workgroups per stream for the largest query count
     int maxq = 1;
@@ -722,9 +692,9 @@ int32_t loam_odometry_solve(loam_odometry* h) {
   k_od_build<<<B * 2, OD_BUILD_THREADS, 0, st>>>(D);
   LOAM_HIP(hipGetLastError());
   LOAM_HIP(hipEventRecord(h->ev[1], st));
-  LOAM_HIP(hipMemcpyAsync(h->hf_pin, D.fr, sizeof(OdomFrame) * B, hipMemcpyDeviceToHost, st));
+  LOAM_HIP(hipMemcpyAsync(h->hf_pin.data(), D.fr, sizeof(OdomFrame) * B, hipMemcpyDeviceToHost, st));
   LOAM_HIP(hipStreamSynchronize(st));
-  std::memcpy(h->hf.data(), h->hf_pin, sizeof(OdomFrame) * B);
+  std::memcpy(h->hf.data(), h->hf_pin.data(), sizeof(OdomFrame) * B);
   float ms = 0.f;
   LOAM_HIP(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
   int err = 0;

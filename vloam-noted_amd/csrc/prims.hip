@@ -7,6 +7,7 @@
 
 #include "cellhash.h"
 #include "common.h"
+#include "device_res.h"
 #include "lm.h"
 #include "voxel.h"
 #include "voxel_hot.h"
@@ -178,23 +179,17 @@ __global__ void k_knn_query(const float4* q, int nq, int k, float radius2, const
   }
 }
 
-// host helpers
-struct DevBuf {
-  void* p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-};
+// host helpers: the untyped scratch of the one-shot entry points, zero-filled synchronously (their
+// kernels run on the null stream)
+using DevBytes = DevBuf<unsigned char>;
 
 template <typename T>
-hipError_t dmalloc(DevBuf& b, size_t n) {
-  hipError_t e = hipMalloc(&b.p, std::max<size_t>(n, 1) * sizeof(T));
-  if (e == hipSuccess) e = hipMemset(b.p, 0, std::max<size_t>(n, 1) * sizeof(T));
-  return e;
+int32_t dmalloc(DevBytes& b, size_t n) {
+  return b.reserve_zeroed(std::max<size_t>(n, 1) * sizeof(T));
 }
 
 struct LmHostRecs {
-  DevBuf type, px, py, pz, a0, a1, a2, b0, b1, b2;
+  DevBytes type, px, py, pz, a0, a1, a2, b0, b1, b2;
   LmRecDev view() {
     return LmRecDev{(int*)type.p, (float*)px.p, (float*)py.p, (float*)pz.p, (double*)a0.p,
                     (double*)a1.p, (double*)a2.p, (double*)b0.p, (double*)b1.p, (double*)b2.p};
@@ -230,16 +225,16 @@ int32_t upload_factors(const double* f, int n, LmHostRecs& R) {
       }
     }
   }
-  LOAM_HIP(dmalloc<int>(R.type, n));
-  LOAM_HIP(dmalloc<float>(R.px, n));
-  LOAM_HIP(dmalloc<float>(R.py, n));
-  LOAM_HIP(dmalloc<float>(R.pz, n));
-  LOAM_HIP(dmalloc<double>(R.a0, n));
-  LOAM_HIP(dmalloc<double>(R.a1, n));
-  LOAM_HIP(dmalloc<double>(R.a2, n));
-  LOAM_HIP(dmalloc<double>(R.b0, n));
-  LOAM_HIP(dmalloc<double>(R.b1, n));
-  LOAM_HIP(dmalloc<double>(R.b2, n));
+  TRY(dmalloc<int>(R.type, n));
+  TRY(dmalloc<float>(R.px, n));
+  TRY(dmalloc<float>(R.py, n));
+  TRY(dmalloc<float>(R.pz, n));
+  TRY(dmalloc<double>(R.a0, n));
+  TRY(dmalloc<double>(R.a1, n));
+  TRY(dmalloc<double>(R.a2, n));
+  TRY(dmalloc<double>(R.b0, n));
+  TRY(dmalloc<double>(R.b1, n));
+  TRY(dmalloc<double>(R.b2, n));
   if (n) {
     LOAM_HIP(hipMemcpy(R.type.p, type.data(), sizeof(int) * n, hipMemcpyHostToDevice));
     LOAM_HIP(hipMemcpy(R.px.p, px.data(), sizeof(float) * n, hipMemcpyHostToDevice));
@@ -276,9 +271,9 @@ int32_t loam_lm_solve(int32_t device, const double* factors, int32_t n, double* 
   const int nblk = 32;
   LmState hS;
   lm_init(hS, x, max_it, true);
-  DevBuf dS, dpart;
-  LOAM_HIP(dmalloc<LmState>(dS, 1));
-  LOAM_HIP(dmalloc<double>(dpart, (size_t)nblk * LM_NACC));
+  DevBytes dS, dpart;
+  TRY(dmalloc<LmState>(dS, 1));
+  TRY(dmalloc<double>(dpart, (size_t)nblk * LM_NACC));
   LOAM_HIP(hipMemcpy(dS.p, &hS, sizeof(LmState), hipMemcpyHostToDevice));
   for (int it = 0; it <= max_it; ++it) {
     k_lm_eval_single<<<nblk, P_LM_THREADS>>>(R.view(), n, (const LmState*)dS.p, (double*)dpart.p);
@@ -315,9 +310,9 @@ int32_t loam_lm_normal_equations(int32_t device, const double* factors, int32_t 
   rc = upload_factors(factors, n, R);
   if (rc != LOAM_OK) return rc;
   const int nchunks = std::max(1, (n + P_LM_CHUNK - 1) / P_LM_CHUNK);
-  DevBuf dx, dpart;
-  LOAM_HIP(dmalloc<double>(dx, 7));
-  LOAM_HIP(dmalloc<double>(dpart, (size_t)nchunks * LM_NACC));
+  DevBytes dx, dpart;
+  TRY(dmalloc<double>(dx, 7));
+  TRY(dmalloc<double>(dpart, (size_t)nchunks * LM_NACC));
   LOAM_HIP(hipMemcpy(dx.p, x, sizeof(double) * 7, hipMemcpyHostToDevice));
   k_lm_eval<<<nchunks, P_LM_THREADS>>>(R.view(), n, (const double*)dx.p, (double*)dpart.p);
   LOAM_HIP(hipGetLastError());
@@ -341,13 +336,13 @@ int32_t loam_voxel_grid(int32_t device, const float* in, int32_t n, float leaf, 
   int32_t rc = ensure_device(device);
   if (rc != LOAM_OK) return rc;
   LOAM_HIP(hipSetDevice(device));
-  DevBuf din, dout, dsp, dsi, dcnt, derr;
-  LOAM_HIP(dmalloc<float4>(din, n));
-  LOAM_HIP(dmalloc<float4>(dout, n));
-  LOAM_HIP(dmalloc<float4>(dsp, n));
-  LOAM_HIP(dmalloc<int>(dsi, n));
-  LOAM_HIP(dmalloc<uint32_t>(dcnt, 1));
-  LOAM_HIP(dmalloc<int>(derr, 1));
+  DevBytes din, dout, dsp, dsi, dcnt, derr;
+  TRY(dmalloc<float4>(din, n));
+  TRY(dmalloc<float4>(dout, n));
+  TRY(dmalloc<float4>(dsp, n));
+  TRY(dmalloc<int>(dsi, n));
+  TRY(dmalloc<uint32_t>(dcnt, 1));
+  TRY(dmalloc<int>(derr, 1));
   if (n) LOAM_HIP(hipMemcpy(din.p, in, sizeof(float4) * n, hipMemcpyHostToDevice));
   VoxSeg S{};
   S.src0 = (const float4*)din.p;
@@ -385,17 +380,17 @@ int32_t loam_voxel_grid_pcl(int32_t device, const float* in, int32_t n, float le
   LOAM_HIP(hipSetDevice(device));
   vh_spin_limit_from_env(device);
   if (n <= VH_MAX_N) {
-    DevBuf din, dout, drk, dhl, dhv, dfp, didx, dcnt, derr;
+    DevBytes din, dout, drk, dhl, dhv, dfp, didx, dcnt, derr;
     const size_t m = std::max(n, 1);
-    LOAM_HIP(dmalloc<float4>(din, m));
-    LOAM_HIP(dmalloc<float4>(dout, m));
-    LOAM_HIP(dmalloc<uint32_t>(drk, m));
-    LOAM_HIP(dmalloc<uint32_t>(dhl, m));
-    LOAM_HIP(dmalloc<uint32_t>(dhv, m + 3));
-    LOAM_HIP(dmalloc<uint32_t>(dfp, m));
-    LOAM_HIP(dmalloc<int>(didx, m));
-    LOAM_HIP(dmalloc<uint32_t>(dcnt, 1));
-    LOAM_HIP(dmalloc<int>(derr, 1));
+    TRY(dmalloc<float4>(din, m));
+    TRY(dmalloc<float4>(dout, m));
+    TRY(dmalloc<uint32_t>(drk, m));
+    TRY(dmalloc<uint32_t>(dhl, m));
+    TRY(dmalloc<uint32_t>(dhv, m + 3));
+    TRY(dmalloc<uint32_t>(dfp, m));
+    TRY(dmalloc<int>(didx, m));
+    TRY(dmalloc<uint32_t>(dcnt, 1));
+    TRY(dmalloc<int>(derr, 1));
     LOAM_HIP(hipMemset(dcnt.p, 0, sizeof(uint32_t)));
     LOAM_HIP(hipMemset(derr.p, 0, sizeof(int)));
     if (n) LOAM_HIP(hipMemcpy(din.p, in, sizeof(float4) * n, hipMemcpyHostToDevice));
@@ -428,17 +423,17 @@ int32_t loam_voxel_grid_pcl(int32_t device, const float* in, int32_t n, float le
     *n_out = (int32_t)cnt;
     return LOAM_OK;
   }
-  DevBuf din, dout, de, da, db, ds, dseg, dcnt, derr;
+  DevBytes din, dout, de, da, db, ds, dseg, dcnt, derr;
   const int cap = ss_cap(n);
-  LOAM_HIP(dmalloc<int>(dseg, 6 * (size_t)cap));
-  LOAM_HIP(dmalloc<float4>(din, n));
-  LOAM_HIP(dmalloc<float4>(dout, n));
-  LOAM_HIP(dmalloc<uint64_t>(de, n));
-  LOAM_HIP(dmalloc<uint32_t>(da, n));
-  LOAM_HIP(dmalloc<uint32_t>(db, n));
-  LOAM_HIP(dmalloc<uint64_t>(ds, n));
-  LOAM_HIP(dmalloc<uint32_t>(dcnt, 1));
-  LOAM_HIP(dmalloc<int>(derr, 1));
+  TRY(dmalloc<int>(dseg, 6 * (size_t)cap));
+  TRY(dmalloc<float4>(din, n));
+  TRY(dmalloc<float4>(dout, n));
+  TRY(dmalloc<uint64_t>(de, n));
+  TRY(dmalloc<uint32_t>(da, n));
+  TRY(dmalloc<uint32_t>(db, n));
+  TRY(dmalloc<uint64_t>(ds, n));
+  TRY(dmalloc<uint32_t>(dcnt, 1));
+  TRY(dmalloc<int>(derr, 1));
   if (n) LOAM_HIP(hipMemcpy(din.p, in, sizeof(float4) * n, hipMemcpyHostToDevice));
   k_voxel_pcl_one<<<1, P_PCL_THREADS>>>((const float4*)din.p, n, leaf, (float4*)dout.p, (uint32_t*)dcnt.p,
                                         (uint64_t*)de.p, (uint32_t*)da.p, (uint32_t*)db.p, (uint64_t*)ds.p,
@@ -466,16 +461,16 @@ int32_t loam_sort_perm(int32_t device, const uint32_t* keys, int32_t n, int32_t 
   if (rc != LOAM_OK) return rc;
   LOAM_HIP(hipSetDevice(device));
   if (n == 0) return LOAM_OK;
-  DevBuf dk, dp, de, da, db, ds, dseg, derr;
+  DevBytes dk, dp, de, da, db, ds, dseg, derr;
   const int cap = ss_cap(n);
-  LOAM_HIP(dmalloc<int>(dseg, 6 * (size_t)cap));
-  LOAM_HIP(dmalloc<uint32_t>(dk, n));
-  LOAM_HIP(dmalloc<int32_t>(dp, n));
-  LOAM_HIP(dmalloc<uint64_t>(de, n));
-  LOAM_HIP(dmalloc<uint32_t>(da, n));
-  LOAM_HIP(dmalloc<uint32_t>(db, n));
-  LOAM_HIP(dmalloc<uint64_t>(ds, n));
-  LOAM_HIP(dmalloc<int>(derr, 1));
+  TRY(dmalloc<int>(dseg, 6 * (size_t)cap));
+  TRY(dmalloc<uint32_t>(dk, n));
+  TRY(dmalloc<int32_t>(dp, n));
+  TRY(dmalloc<uint64_t>(de, n));
+  TRY(dmalloc<uint32_t>(da, n));
+  TRY(dmalloc<uint32_t>(db, n));
+  TRY(dmalloc<uint64_t>(ds, n));
+  TRY(dmalloc<int>(derr, 1));
   LOAM_HIP(hipMemcpy(dk.p, keys, sizeof(uint32_t) * n, hipMemcpyHostToDevice));
   k_sort_perm<<<1, P_PCL_THREADS>>>((const uint32_t*)dk.p, n, (int32_t*)dp.p, (uint64_t*)de.p, (uint32_t*)da.p,
                                     (uint32_t*)db.p, (uint64_t*)ds.p, (int*)dseg.p, cap, n_waves, (int*)derr.p);
@@ -500,16 +495,16 @@ int32_t loam_voxel_merge(int32_t device, const float* fixed, int32_t n0, const f
   if (rc != LOAM_OK) return rc;
   LOAM_HIP(hipSetDevice(device));
   const int32_t n = n0 + n1;
-  DevBuf dc, da, dout, dsp, dsi, doff, dcnt, derr, dm;
-  LOAM_HIP(dmalloc<float4>(dc, n0));
-  LOAM_HIP(dmalloc<float4>(da, n1));
-  LOAM_HIP(dmalloc<float4>(dout, n));
-  LOAM_HIP(dmalloc<float4>(dsp, n));
-  LOAM_HIP(dmalloc<int>(dsi, n));
-  LOAM_HIP(dmalloc<uint32_t>(doff, 1));
-  LOAM_HIP(dmalloc<uint32_t>(dcnt, 1));
-  LOAM_HIP(dmalloc<int>(derr, 1));
-  LOAM_HIP(dmalloc<int>(dm, 1));
+  DevBytes dc, da, dout, dsp, dsi, doff, dcnt, derr, dm;
+  TRY(dmalloc<float4>(dc, n0));
+  TRY(dmalloc<float4>(da, n1));
+  TRY(dmalloc<float4>(dout, n));
+  TRY(dmalloc<float4>(dsp, n));
+  TRY(dmalloc<int>(dsi, n));
+  TRY(dmalloc<uint32_t>(doff, 1));
+  TRY(dmalloc<uint32_t>(dcnt, 1));
+  TRY(dmalloc<int>(derr, 1));
+  TRY(dmalloc<int>(dm, 1));
   if (n0) LOAM_HIP(hipMemcpy(dc.p, fixed, sizeof(float4) * n0, hipMemcpyHostToDevice));
   if (n1) LOAM_HIP(hipMemcpy(da.p, added, sizeof(float4) * n1, hipMemcpyHostToDevice));
   VoxSeg S{};
@@ -572,21 +567,21 @@ int32_t loam_knn_radius(int32_t device, const float* pts, int32_t n, const float
   }
   uint32_t T = 1;
   while (T < (uint32_t)std::max(2 * n, 64)) T <<= 1;
-  DevBuf dp, dq, dorig, dhk, dhc, dhs, dqt, dps, dpr, dsp, dcur, derr, didx, dd2;
-  LOAM_HIP(dmalloc<float4>(dp, n));
-  LOAM_HIP(dmalloc<float4>(dq, nq));
-  LOAM_HIP(dmalloc<int>(dorig, 3));
-  LOAM_HIP(dmalloc<unsigned long long>(dhk, T));
-  LOAM_HIP(dmalloc<unsigned long long>(dhc, T));
-  LOAM_HIP(dmalloc<uint32_t>(dhs, T));
-  LOAM_HIP(dmalloc<uint4>(dqt, T));
-  LOAM_HIP(dmalloc<uint32_t>(dps, n));
-  LOAM_HIP(dmalloc<uint32_t>(dpr, n));
-  LOAM_HIP(dmalloc<float4>(dsp, n));
-  LOAM_HIP(dmalloc<uint32_t>(dcur, 1));
-  LOAM_HIP(dmalloc<int>(derr, 1));
-  LOAM_HIP(dmalloc<int>(didx, (size_t)nq * k));
-  LOAM_HIP(dmalloc<float>(dd2, (size_t)nq * k));
+  DevBytes dp, dq, dorig, dhk, dhc, dhs, dqt, dps, dpr, dsp, dcur, derr, didx, dd2;
+  TRY(dmalloc<float4>(dp, n));
+  TRY(dmalloc<float4>(dq, nq));
+  TRY(dmalloc<int>(dorig, 3));
+  TRY(dmalloc<unsigned long long>(dhk, T));
+  TRY(dmalloc<unsigned long long>(dhc, T));
+  TRY(dmalloc<uint32_t>(dhs, T));
+  TRY(dmalloc<uint4>(dqt, T));
+  TRY(dmalloc<uint32_t>(dps, n));
+  TRY(dmalloc<uint32_t>(dpr, n));
+  TRY(dmalloc<float4>(dsp, n));
+  TRY(dmalloc<uint32_t>(dcur, 1));
+  TRY(dmalloc<int>(derr, 1));
+  TRY(dmalloc<int>(didx, (size_t)nq * k));
+  TRY(dmalloc<float>(dd2, (size_t)nq * k));
   if (n) LOAM_HIP(hipMemcpy(dp.p, pts, sizeof(float4) * n, hipMemcpyHostToDevice));
   if (nq) LOAM_HIP(hipMemcpy(dq.p, queries, sizeof(float4) * nq, hipMemcpyHostToDevice));
   LOAM_HIP(hipMemcpy(dorig.p, origin, sizeof(origin), hipMemcpyHostToDevice));

@@ -28,9 +28,11 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <memory>
 #include <vector>
 
 #include "common.h"
+#include "device_res.h"
 #include "libm_f32.h"
 #include "stdsort.h"
 #include "voxel.h"
@@ -944,10 +946,10 @@ __global__ void k_sr_gather(const SrDev* __restrict__ Ds) {
 using namespace loam;
 
 struct loam_scanreg {
+  DevStream st;  // first: destroyed after everything below
   loam_params P;
   int dev = 0;
-  hipStream_t st = nullptr;
-  hipEvent_t ev[2] = {nullptr, nullptr};
+  DevEvent ev[2];
   // frames per launch sequence (loam_scanreg_create_batch; 1 for loam_scanreg_create): every
   // per-frame buffer exists nb times, Dv[f] points at frame f's; D is frame 0's (the single-frame
   // calls)
@@ -955,44 +957,20 @@ struct loam_scanreg {
   std::vector<SrDev> Dv;
   SrDev D{};
   SrDev* d_Ds = nullptr;      // [nb] the launch's frame views (kernel argument arrays)
-  SrDev* h_Ds = nullptr;      // [nb] page-locked staging of d_Ds
+  PinnedArray<SrDev> h_Ds;    // [nb] page-locked staging of d_Ds
   int nf = 0;                 // frames of the last launch
   std::vector<SrFrame> hfv;   // [nb] their records after the wait
   SrFrame hf{};               // frame 0's
   float* d_in = nullptr;      // [nb][cap][4] staging of host input
-  float* h_pinned = nullptr;  // loam_scanreg_host_buffer: page-locked ingest buffer (cap x 4 floats)
-  SrFrame* hf_pinned = nullptr;  // [nb] D2H target of the frame records (page-locked: the copy stays async)
+  PinnedArray<float> h_pinned;  // loam_scanreg_host_buffer: page-locked ingest buffer (cap x 4 floats)
+  PinnedArray<SrFrame> hf_pinned;  // [nb] D2H target of the frame records (page-locked: the copy stays async)
   int pending = 0;            // loam_scanreg_input_async launched, loam_scanreg_wait not yet called
   int pending_stride = 4;
   const float* pending_xyz = nullptr;
-  std::vector<void*> allocs;
+  DevPool pool;
   float ms = 0.f;
+  ~loam_scanreg() { (void)hipStreamSynchronize(st); }  // an input_async still in flight
 };
-
-namespace {
-template <typename T>
-int32_t sralloc(loam_scanreg* h, T** p, size_t n) {
-  void* q = nullptr;
-  LOAM_HIP(hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)));
-  // zero on the handle's own (non-blocking) stream: a null-stream memset is not ordered
-  // before this stream's kernels; create() synchronizes the stream before returning
-  LOAM_HIP(hipMemsetAsync(q, 0, std::max<size_t>(n, 1) * sizeof(T), h->st));
-  h->allocs.push_back(q);
-  *p = reinterpret_cast<T*>(q);
-  return LOAM_OK;
-}
-void sr_free(loam_scanreg* h) {
-  if (h->st) (void)hipStreamSynchronize(h->st);  // an input_async still in flight
-  if (h->h_pinned) (void)hipHostFree(h->h_pinned);
-  if (h->hf_pinned) (void)hipHostFree(h->hf_pinned);
-  if (h->h_Ds) (void)hipHostFree(h->h_Ds);
-  for (void* p : h->allocs) (void)hipFree(p);
-  h->allocs.clear();
-  for (auto& e : h->ev)
-    if (e) (void)hipEventDestroy(e);
-  if (h->st) (void)hipStreamDestroy(h->st);
-}
-}  // namespace
 
 extern "C" {
 
@@ -1003,14 +981,12 @@ int32_t loam_scanreg_create(const loam_params* p, int32_t device, loam_scanreg**
 int32_t loam_scanreg_create_batch(const loam_params* p, int32_t device, int32_t max_frames, loam_scanreg** out) {
   if (!out || max_frames < 1) return LOAM_ERR_ARG;
   *out = nullptr;
-  int32_t rc = ensure_device(device);
-  if (rc != LOAM_OK) return rc;
+  TRY(ensure_device(device));
   LOAM_HIP(hipSetDevice(device));
   vh_spin_limit_from_env(device);
-  auto* h = new loam_scanreg;
+  std::unique_ptr<loam_scanreg> h(new loam_scanreg);
   if (p) h->P = *p; else loam_params_default(&h->P);
   if (h->P.scan_line != 16 && h->P.scan_line != 32 && h->P.scan_line != 64) {
-    delete h;
     set_error("only support velodyne with 16, 32 or 64 scan line (scan_registration.cpp:58-61)");
     return LOAM_ERR_ARG;
   }
@@ -1025,53 +1001,47 @@ int32_t loam_scanreg_create_batch(const loam_params* p, int32_t device, int32_t 
   D.n_scans = h->P.scan_line;
   D.min_range = (float)h->P.minimum_range;
   const int nblocks = (cap + SR_BLOCK - 1) / SR_BLOCK;
-  auto fail = [&](int32_t r) {
-    sr_free(h);
-    delete h;
-    return r;
-  };
-  if (hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking) != hipSuccess) return fail(LOAM_ERR_HIP);
-  for (auto& e : h->ev)
-    if (hipEventCreate(&e) != hipSuccess) return fail(LOAM_ERR_HIP);
+  TRY(h->st.create());
+  for (auto& e : h->ev) TRY(e.create());
   // every per-frame buffer: one allocation of nb copies, frame f's at f * n
-#define SRA(field, n)                                                      \
-  do {                                                                     \
-    const size_t n_ = (n);                                                 \
-    if ((rc = sralloc(h, &D.field, n_ * nb)) != LOAM_OK) return fail(rc);  \
-    for (int f = 0; f < nb; ++f) h->Dv[f].field = D.field + f * n_;        \
-  } while (0)
-  if ((rc = sralloc(h, &h->d_in, (size_t)cap * 4 * nb)) != LOAM_OK) return fail(rc);
-  SRA(fr, 1);
-  SRA(ring_of, cap);
-  SRA(blk_hist, (size_t)SR_MAX_RINGS * nblocks);
-  SRA(blk_off, (size_t)SR_MAX_RINGS * nblocks);
-  SRA(blk_aux, (size_t)3 * nblocks);
-  SRA(cloud, cap);
-  SRA(curv, cap);
-  SRA(label, cap);
-  SRA(ring_sharp, SR_MAX_RINGS * 6 * SR_SHARP);
-  SRA(ring_less_sharp, SR_MAX_RINGS * 6 * SR_LESS_SHARP);
-  SRA(ring_flat, SR_MAX_RINGS * 6 * SR_FLAT);
-  SRA(less_flat_scan, cap);
-  SRA(less_flat_ds, cap);
-  SRA(vx_pts, cap);
-  SRA(vx_idx, cap);
-  for (int k = 1; k < 5; ++k) SRA(out[k], cap);
-  SRA(ss_e, cap);
-  SRA(ss_a, cap);
-  SRA(ss_b, cap);
-  SRA(ss_s, cap);
-  SRA(ss_seg, (size_t)SR_MAX_RINGS * 6 * SR_SS_GSEG);
-  if ((rc = sralloc(h, &D.dbg, LOAM_SR_DEBUG_COUNTERS)) != LOAM_OK) return fail(rc);  // shared by the frames
+  auto frames = [&](auto field, size_t n) -> int32_t {
+    TRY(h->pool.alloc(&(D.*field), n * nb, h->st));
+    for (int f = 0; f < nb; ++f) h->Dv[f].*field = D.*field + f * n;
+    return LOAM_OK;
+  };
+  TRY(h->pool.alloc(&h->d_in, (size_t)cap * 4 * nb, h->st));
+  TRY(frames(&SrDev::fr, 1));
+  TRY(frames(&SrDev::ring_of, cap));
+  TRY(frames(&SrDev::blk_hist, (size_t)SR_MAX_RINGS * nblocks));
+  TRY(frames(&SrDev::blk_off, (size_t)SR_MAX_RINGS * nblocks));
+  TRY(frames(&SrDev::blk_aux, (size_t)3 * nblocks));
+  TRY(frames(&SrDev::cloud, cap));
+  TRY(frames(&SrDev::curv, cap));
+  TRY(frames(&SrDev::label, cap));
+  TRY(frames(&SrDev::ring_sharp, SR_MAX_RINGS * 6 * SR_SHARP));
+  TRY(frames(&SrDev::ring_less_sharp, SR_MAX_RINGS * 6 * SR_LESS_SHARP));
+  TRY(frames(&SrDev::ring_flat, SR_MAX_RINGS * 6 * SR_FLAT));
+  TRY(frames(&SrDev::less_flat_scan, cap));
+  TRY(frames(&SrDev::less_flat_ds, cap));
+  TRY(frames(&SrDev::vx_pts, cap));
+  TRY(frames(&SrDev::vx_idx, cap));
+  for (int k = 1; k < 5; ++k) {
+    TRY(h->pool.alloc(&D.out[k], (size_t)cap * nb, h->st));
+    for (int f = 0; f < nb; ++f) h->Dv[f].out[k] = D.out[k] + (size_t)f * cap;
+  }
+  TRY(frames(&SrDev::ss_e, cap));
+  TRY(frames(&SrDev::ss_a, cap));
+  TRY(frames(&SrDev::ss_b, cap));
+  TRY(frames(&SrDev::ss_s, cap));
+  TRY(frames(&SrDev::ss_seg, (size_t)SR_MAX_RINGS * 6 * SR_SS_GSEG));
+  TRY(h->pool.alloc(&D.dbg, LOAM_SR_DEBUG_COUNTERS, h->st));  // shared by the frames
   {
     const char* penv = std::getenv("LOAM_PHASE_COUNTERS");
     D.pdbg = (penv && std::atoi(penv) > 0) ? D.dbg : nullptr;
   }
-#undef SRA
-  if ((rc = sralloc(h, &h->d_Ds, nb)) != LOAM_OK) return fail(rc);
-  if (hipHostMalloc(reinterpret_cast<void**>(&h->h_Ds), sizeof(SrDev) * nb, hipHostMallocDefault) != hipSuccess ||
-      hipHostMalloc(reinterpret_cast<void**>(&h->hf_pinned), sizeof(SrFrame) * nb, hipHostMallocDefault) != hipSuccess)
-    return fail(LOAM_ERR_HIP);
+  TRY(h->pool.alloc(&h->d_Ds, nb, h->st));
+  TRY(h->h_Ds.assign(nb, SrDev{}));
+  TRY(h->hf_pinned.assign(nb, SrFrame{}));
   D.out[0] = D.cloud;
   D.sort_ind = nullptr;
   for (int f = 0; f < nb; ++f) {  // the scalars and the shared pointers
@@ -1085,15 +1055,14 @@ int32_t loam_scanreg_create_batch(const loam_params* p, int32_t device, int32_t 
     V.sort_ind = nullptr;
   }
   h->Dv[0] = D;
-  if (hipStreamSynchronize(h->st) != hipSuccess) return fail(LOAM_ERR_HIP);
-  *out = h;
+  LOAM_HIP(hipStreamSynchronize(h->st));
+  *out = h.release();
   return LOAM_OK;
 }
 
 int32_t loam_scanreg_destroy(loam_scanreg* h) {
   if (!h) return LOAM_ERR_ARG;
   (void)hipSetDevice(h->dev);
-  sr_free(h);
   delete h;
   return LOAM_OK;
 }
@@ -1141,7 +1110,7 @@ static int32_t sr_launch_frames(loam_scanreg* h, int nf, const float* const* xyz
     }
     h->h_Ds[f] = D;
   }
-  LOAM_HIP(hipMemcpyAsync(h->d_Ds, h->h_Ds, sizeof(SrDev) * nf, hipMemcpyHostToDevice, st));
+  LOAM_HIP(hipMemcpyAsync(h->d_Ds, h->h_Ds.data(), sizeof(SrDev) * nf, hipMemcpyHostToDevice, st));
   static_assert(sizeof(SrFrame) % 4 == 0, "k_sr_init writes the record by words");
   LOAM_HIP(hipEventRecord(h->ev[0], st));
   const SrDev* Ds = h->d_Ds;
@@ -1159,7 +1128,7 @@ static int32_t sr_launch_frames(loam_scanreg* h, int nf, const float* const* xyz
     LOAM_HIP(hipGetLastError());
   }
   LOAM_HIP(hipEventRecord(h->ev[1], st));
-  LOAM_HIP(hipMemcpyAsync(h->hf_pinned, h->Dv[0].fr, sizeof(SrFrame) * nf, hipMemcpyDeviceToHost, st));
+  LOAM_HIP(hipMemcpyAsync(h->hf_pinned.data(), h->Dv[0].fr, sizeof(SrFrame) * nf, hipMemcpyDeviceToHost, st));
   h->pending = 1;
   h->nf = nf;
   h->pending_xyz = h->h_Ds[0].xyz;
@@ -1215,12 +1184,11 @@ int32_t loam_scanreg_input_device(loam_scanreg* h, const float* d_xyz, int32_t n
 
 int32_t loam_scanreg_host_buffer(loam_scanreg* h, float** ptr, int32_t* cap_points) {
   if (!h || !ptr) return LOAM_ERR_ARG;
-  if (!h->h_pinned) {
+  if (!h->h_pinned.data()) {
     LOAM_HIP(hipSetDevice(h->dev));
-    LOAM_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->h_pinned), sizeof(float) * 4 * (size_t)h->D.cap,
-                           hipHostMallocDefault));
+    TRY(h->h_pinned.assign(4 * (size_t)h->D.cap, 0.f));
   }
-  *ptr = h->h_pinned;
+  *ptr = h->h_pinned.data();
   if (cap_points) *cap_points = h->D.cap;
   return LOAM_OK;
 }

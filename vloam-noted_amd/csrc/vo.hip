@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "common.h"
+#include "device_res.h"
 #include "lm.h"
 #include "vo_dev.h"
 
@@ -242,37 +243,20 @@ int32_t loam_vo_solve(int32_t device, int32_t n_problems, const int32_t* offsets
   if (nf > 0 && !factors) return LOAM_ERR_ARG;
   TRY(ensure_device(device));
   LOAM_HIP(hipSetDevice(device));
-  double* d_f = nullptr;
-  double* d_x = nullptr;
-  int* d_off = nullptr;
-  loam_lm_stats* d_s = nullptr;
-  auto cleanup = [&]() {
-    if (d_f) (void)hipFree(d_f);
-    if (d_x) (void)hipFree(d_x);
-    if (d_off) (void)hipFree(d_off);
-    if (d_s) (void)hipFree(d_s);
-  };
-  hipError_t e = hipMalloc(&d_f, sizeof(double) * 10 * std::max(nf, 1));
-  if (e == hipSuccess) e = hipMalloc(&d_x, sizeof(double) * 6 * n_problems);
-  if (e == hipSuccess) e = hipMalloc(&d_off, sizeof(int) * (n_problems + 1));
-  if (e == hipSuccess) e = hipMalloc(&d_s, sizeof(loam_lm_stats) * n_problems);
-  if (e == hipSuccess && nf) e = hipMemcpy(d_f, factors, sizeof(double) * 10 * nf, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_x, x, sizeof(double) * 6 * n_problems, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_off, offsets, sizeof(int) * (n_problems + 1), hipMemcpyHostToDevice);
-  int32_t launched = LOAM_OK;  // a failed launch has set the error text itself
-  if (e == hipSuccess) launched = vo_solve_launch(d_f, d_off, 1, d_x, max_iterations, d_s, n_problems, nullptr);
-  if (launched != LOAM_OK) {
-    cleanup();
-    return launched;
-  }
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(x, d_x, sizeof(double) * 6 * n_problems, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && st) e = hipMemcpy(st, d_s, sizeof(loam_lm_stats) * n_problems, hipMemcpyDeviceToHost);
-  cleanup();
-  if (e != hipSuccess) {
-    set_error(std::string("loam_vo_solve: ") + hipGetErrorString(e));
-    return LOAM_ERR_HIP;
-  }
+  DevBuf<double> d_f, d_x;
+  DevBuf<int> d_off;
+  DevBuf<loam_lm_stats> d_s;
+  TRY(d_f.reserve(10 * (size_t)std::max(nf, 1)));
+  TRY(d_x.reserve(6 * (size_t)n_problems));
+  TRY(d_off.reserve((size_t)n_problems + 1));
+  TRY(d_s.reserve(n_problems));
+  if (nf) LOAM_HIP(hipMemcpy(d_f, factors, sizeof(double) * 10 * nf, hipMemcpyHostToDevice));
+  LOAM_HIP(hipMemcpy(d_x, x, sizeof(double) * 6 * n_problems, hipMemcpyHostToDevice));
+  LOAM_HIP(hipMemcpy(d_off, offsets, sizeof(int) * (n_problems + 1), hipMemcpyHostToDevice));
+  TRY(vo_solve_launch(d_f, d_off, 1, d_x, max_iterations, d_s, n_problems, nullptr));
+  LOAM_HIP(hipDeviceSynchronize());
+  LOAM_HIP(hipMemcpy(x, d_x, sizeof(double) * 6 * n_problems, hipMemcpyDeviceToHost));
+  if (st) LOAM_HIP(hipMemcpy(st, d_s, sizeof(loam_lm_stats) * n_problems, hipMemcpyDeviceToHost));
   return LOAM_OK;
 }
 

@@ -29,10 +29,11 @@
 // vo.vo_factors' definition (the reference's float colPivHouseholderQr is not pinned).
 #include <algorithm>
 #include <cmath>
+#include <memory>
 #include <vector>
 
-#include "common.h"
 #include "depth_dev.h"
+#include "device_res.h"
 #include "vo_dev.h"
 
 namespace loam {
@@ -280,6 +281,7 @@ __global__ void __launch_bounds__(VA_THREADS) k_vo_assemble(const VfPair* pairs,
 using namespace loam;
 
 struct loam_vo_frames {
+  DevStream st;  // first: destroyed after everything below
   int dev = 0;
   int P = 0, K = 0;       // pairs, keypoints per image
   int W = 0, WP = 0;      // descriptor dwords given / stored
@@ -292,7 +294,7 @@ struct loam_vo_frames {
   std::vector<double> x0, x;    // [P][6] initial values / results
   std::vector<loam_lm_stats> lm;
   std::vector<VfCount> cnt;
-  std::vector<void*> allocs;
+  DevPool pool;
   VfPair* d_pairs = nullptr;
   uint32_t *d_desc0 = nullptr, *d_desc1 = nullptr;  // [P][K][WP]
   float2 *d_kp0 = nullptr, *d_kp1 = nullptr;        // [P][K]
@@ -305,31 +307,12 @@ struct loam_vo_frames {
   double* d_x = nullptr;                            // [P][6]
   loam_lm_stats* d_lm = nullptr;
   VfCount* d_cnt = nullptr;
-  hipStream_t st = nullptr;
-  hipEvent_t ev[2] = {nullptr, nullptr};
+  DevEvent ev[2];
   float ms = 0.f;
+  ~loam_vo_frames() { (void)hipStreamSynchronize(st); }
 };
 
 namespace {
-
-template <typename T>
-int32_t vf_alloc(loam_vo_frames* h, T** p, size_t n) {
-  void* q = nullptr;
-  const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
-  LOAM_HIP(hipMalloc(&q, bytes));
-  LOAM_HIP(hipMemsetAsync(q, 0, bytes, h->st));
-  h->allocs.push_back(q);
-  *p = reinterpret_cast<T*>(q);
-  return LOAM_OK;
-}
-
-void vf_free(loam_vo_frames* h) {
-  for (void* p : h->allocs) (void)hipFree(p);
-  h->allocs.clear();
-  for (auto& e : h->ev)
-    if (e) (void)hipEventDestroy(e);
-  if (h->st) (void)hipStreamDestroy(h->st);
-}
 
 // P K = L U with partial pivoting; false when K is singular to working precision
 bool vf_factor(const float* P_rect0, VfCam* C) {
@@ -417,7 +400,7 @@ int32_t loam_vo_frames_create(const loam_vo_frames_params* p, loam_depth* depth,
   int dev = 0;
   TRY(depth_device_view(depth, &D, &dev));
   LOAM_HIP(hipSetDevice(dev));
-  auto* h = new loam_vo_frames;
+  std::unique_ptr<loam_vo_frames> h(new loam_vo_frames);
   h->dev = dev;
   h->depth = depth;
   h->prm = *p;
@@ -427,48 +410,38 @@ int32_t loam_vo_frames_create(const loam_vo_frames_params* p, loam_depth* depth,
   h->W = p->desc_bytes / 4;
   h->WP = h->W <= 8 ? 8 : 16;
   h->S_cap = std::max(1, std::min(VM_MAX_SLICES, 256 / n_pairs));
-  auto fail = [&](int32_t r) {
-    vf_free(h);
-    delete h;
-    return r;
-  };
-  if (hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking) != hipSuccess) return fail(LOAM_ERR_HIP);
-  for (auto& e : h->ev)
-    if (hipEventCreate(&e) != hipSuccess) return fail(LOAM_ERR_HIP);
+  TRY(h->st.create());
+  for (auto& e : h->ev) TRY(e.create());
   const size_t P = n_pairs, K = h->K;
-  int32_t rc = LOAM_OK;
-#define VA(ptr, n) \
-  if ((rc = vf_alloc(h, &(ptr), (n))) != LOAM_OK) return fail(rc)
-  VA(h->d_pairs, P);
-  VA(h->d_desc0, P * K * h->WP);
-  VA(h->d_desc1, P * K * h->WP);
-  VA(h->d_kp0, P * K);
-  VA(h->d_kp1, P * K);
-  VA(h->d_status, P * K);
-  VA(h->d_part, P * h->S_cap * K);
-  VA(h->d_matches, P * K);
-  VA(h->d_records, P * K * 10);
-  VA(h->d_depth0, P * K);
-  VA(h->d_off, P * 2);
-  VA(h->d_x, P * 6);
-  VA(h->d_lm, P);
-  VA(h->d_cnt, P);
-#undef VA
+  auto alloc = [&](auto& ptr, size_t n) { return h->pool.alloc(&ptr, n, h->st); };
+  TRY(alloc(h->d_pairs, P));
+  TRY(alloc(h->d_desc0, P * K * h->WP));
+  TRY(alloc(h->d_desc1, P * K * h->WP));
+  TRY(alloc(h->d_kp0, P * K));
+  TRY(alloc(h->d_kp1, P * K));
+  TRY(alloc(h->d_status, P * K));
+  TRY(alloc(h->d_part, P * h->S_cap * K));
+  TRY(alloc(h->d_matches, P * K));
+  TRY(alloc(h->d_records, P * K * 10));
+  TRY(alloc(h->d_depth0, P * K));
+  TRY(alloc(h->d_off, P * 2));
+  TRY(alloc(h->d_x, P * 6));
+  TRY(alloc(h->d_lm, P));
+  TRY(alloc(h->d_cnt, P));
   h->pairs.assign(P, VfPair{});
   h->solved.assign(P, 0);
   h->x0.assign(P * 6, 0.0);
   h->x.assign(P * 6, 0.0);
   h->lm.assign(P, loam_lm_stats{});
   h->cnt.assign(P, VfCount{});
-  if (hipStreamSynchronize(h->st) != hipSuccess) return fail(LOAM_ERR_HIP);
-  *out = h;
+  LOAM_HIP(hipStreamSynchronize(h->st));
+  *out = h.release();
   return LOAM_OK;
 }
 
 int32_t loam_vo_frames_destroy(loam_vo_frames* h) {
   if (!h) return LOAM_ERR_ARG;
   (void)hipSetDevice(h->dev);
-  vf_free(h);
   delete h;
   return LOAM_OK;
 }

@@ -83,6 +83,7 @@ SIGNATURES = {
     "loam_params_default": (None, [ctypes.POINTER(Params)]),
     "loam_last_error": (ctypes.c_char_p, []),
     "loam_version": (c_i32, []),
+    "loam_debug_live_resources": (c_i32, [ctypes.POINTER(ctypes.c_int64 * 4)]),
     "loam_scanreg_create": (c_i32, [ctypes.POINTER(Params), c_i32, ctypes.POINTER(vp)]),
     "loam_scanreg_destroy": (c_i32, [vp]),
     "loam_scanreg_input": (c_i32, [vp, vp, c_i32, c_i32]),
