@@ -366,6 +366,18 @@ int32_t loam_mapper_cube_count(loam_mapper* h, int32_t stream, int32_t which, in
 int32_t loam_mapper_stack_copy(loam_mapper* h, int32_t stream, int32_t which, float* out, int32_t cap);
 int32_t loam_mapper_cube_copy(loam_mapper* h, int32_t stream, int32_t which, int32_t cube,
                               float* out);
+/* for parity tests of the correspondence kernels: what the second outer round of the last solve
+ * (laser_mapping.cpp:545-699) left on the device for every query, corner stack first, then surf
+ * stack.  type: the record type (0 none, 1 line, 3 plane); records: 10 doubles per query (type,
+ * curr_point[3], a[3], b[3]; line: a = point_a, b = the unit vector of point_a - point_b; plane:
+ * a = unit normal, b[0] = negative_OA_dot_norm; type 0: a = b = 0); nbr_xyz: 5 x 3 floats per query,
+ * the 5 nearest map points in nearestKSearch order, NaN where the 5th is not within 1 m (:557,
+ * :642); x0 (may be NULL): the 7 pose values (q xyzw, t) that round's search transformed the queries
+ * with.  A frame that was not optimised (:514) has type 0 and NaN neighbours throughout.  Copies
+ * when cap >= the count; returns the count.  Valid until the stream's next input, reset or state
+ * change. */
+int32_t loam_mapper_corr_copy(loam_mapper* h, int32_t stream, double* x0, int32_t* type, double* records,
+                              float* nbr_xyz, int32_t cap);
 int32_t loam_mapper_cube_set(loam_mapper* h, int32_t stream, int32_t which, int32_t cube,
                              const float* pts, int32_t n);
 /* /laser_cloud_map (laser_mapping.cpp:884-899): corner cube 0, surf cube 0, corner cube 1, ...
@@ -597,6 +609,12 @@ int32_t loam_voxel_merge(int32_t device, const float* fixed, int32_t n0, const f
  * idx/d2 sorted ascending; missing entries idx = -1 */
 int32_t loam_knn_radius(int32_t device, const float* pts, int32_t n, const float* queries,
                         int32_t nq, int32_t k, float radius2, int32_t* idx, float* d2);
+/* the mapper's line (which 0, laser_mapping.cpp:557-603) or plane (which 1, :642-680) fit of n sets
+ * of 5 neighbours (nbrs: n x 5 x 3 floats, nearestKSearch order), with the device functions and
+ * compiler flags of the mapper's own kernel.  ok[i]: the fit passed its test; a, b (n x 3 doubles
+ * each): what the mapper's factor record gets then (loam_mapper_corr_copy), zeros otherwise */
+int32_t loam_corr_geometry(int32_t device, const float* nbrs, int32_t n, int32_t which, int32_t* ok,
+                           double* a, double* b);
 
 #ifdef __cplusplus
 }

@@ -22,7 +22,8 @@ def declared():
 def test_header_declares_the_api():
     names = declared()
     for must in ("loam_scanreg_create", "loam_scanreg_input", "loam_mapper_create", "loam_mapper_input",
-                 "loam_mapper_solve", "loam_mapper_pose", "loam_lm_solve", "loam_voxel_grid"):
+                 "loam_mapper_solve", "loam_mapper_pose", "loam_lm_solve", "loam_voxel_grid",
+                 "loam_mapper_corr_copy", "loam_corr_geometry"):
         assert must in names
 
 
@@ -142,3 +143,6 @@ def test_new_entry_points_validate_arguments():
     bad = (ctypes.c_int32 * 2)(1, 0)
     assert L.loam_vo_solve(0, 1, bad, None, x, 100, None) == -1        # offsets must start at 0
     assert L.loam_vo_solve(0, 0, None, None, None, 100, None) == 0      # nothing to do
+    assert L.loam_corr_geometry(0, None, 1, 0, None, None, None) == -1  # neighbour sets missing
+    assert L.loam_corr_geometry(0, None, 0, 2, None, None, None) == -1  # which: 0 line, 1 plane
+    assert L.loam_mapper_corr_copy(None, 0, None, None, None, None, 0) == -1

@@ -1699,6 +1699,32 @@ int32_t loam_mapper_stack_copy(loam_mapper* h, int32_t s, int32_t which, float* 
   return n;
 }
 
+int32_t loam_mapper_corr_copy(loam_mapper* h, int32_t s, double* x0, int32_t* type, double* records, float* nbr_xyz,
+                              int32_t cap) {
+  SETTLE(h);
+  TRY(check_stream(h, s));
+  if (cap < 0 || (cap > 0 && (!type || !records || !nbr_xyz))) return LOAM_ERR_ARG;
+  LOAM_HIP(hipSetDevice(h->dev));
+  const StreamFrame& F = h->hf[s];
+  const int32_t n = F.nc_stack + F.ns_stack;
+  if (x0) std::copy(F.knn_pose, F.knn_pose + 7, x0);
+  if (n > cap || n == 0) return n;  // the count only
+  DevBuf<int> dt;
+  DevBuf<double> dr;
+  DevBuf<float> dn;
+  TRY(dt.reserve(n));
+  TRY(dr.reserve((size_t)n * 10));
+  TRY(dn.reserve((size_t)n * 15));
+  k_corr_gather<<<std::min(256, (n + 255) / 256), 256, 0, h->st>>>(h->D, s, F.nc_stack, n, F.optimize, F.arena_active[0],
+                                                                  F.arena_active[1], dt, dr, dn);
+  LOAM_HIP(hipGetLastError());
+  LOAM_HIP(hipMemcpyAsync(type, dt, sizeof(int) * n, hipMemcpyDeviceToHost, h->st));
+  LOAM_HIP(hipMemcpyAsync(records, dr, sizeof(double) * n * 10, hipMemcpyDeviceToHost, h->st));
+  LOAM_HIP(hipMemcpyAsync(nbr_xyz, dn, sizeof(float) * n * 15, hipMemcpyDeviceToHost, h->st));
+  LOAM_HIP(hipStreamSynchronize(h->st));
+  return n;
+}
+
 int32_t loam_mapper_cube_set(loam_mapper* h, int32_t s, int32_t which, int32_t cube, const float* pts, int32_t n) {
   SETTLE(h);
   TRY(check_stream(h, s));

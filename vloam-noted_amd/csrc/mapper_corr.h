@@ -67,7 +67,11 @@ __global__ void __launch_bounds__(CORR_THREADS) __attribute__((amdgpu_waves_per_
 #pragma unroll
   for (int i = 0; i < 7; ++i) X[i] = F.pose[i];
   if (blk == 0 && threadIdx.x < LM_SYNC_WORDS) D.lm_sync[((size_t)s * 2 + round) * LM_SYNC_WORDS + threadIdx.x] = 0;
-  if (blk == 0 && threadIdx.x == 0) lm_init(F.lm[round], X, 4, F.optimize != 0);
+  if (blk == 0 && threadIdx.x == 0) {
+    lm_init(F.lm[round], X, 4, F.optimize != 0);
+#pragma unroll
+    for (int i = 0; i < 7; ++i) F.knn_pose[i] = X[i];
+  }
   if (!F.optimize) return;  // k_geom types every record 0
   const int tid = threadIdx.x;
   const int c0 = F.center[0] - 2, c1 = F.center[1] - 2, c2 = F.center[2] - 1;
@@ -330,6 +334,41 @@ __global__ void __launch_bounds__(CORR_THREADS) k_geom(MapperDev D, int round) {
   if ((threadIdx.x & 63) == 0) {
     if (we) atomicAdd(&F.corner_num[round], (int)we);
     if (wp) atomicAdd(&F.surf_num[round], (int)wp);
+  }
+}
+
+// loam_mapper_corr_copy: what the last round left for the nq = nc + ns queries of stream s, in stack
+// order: type[nq], rec[nq][10] = (type, po, a, b) as loam_lm_solve takes them, nbr[nq][5][3] the
+// accepted neighbours in kNN order (NaN where the 1 m test rejected them).  The neighbours are read
+// as k_geom reads them: through knn_id in the cell-sorted arena `active`, sharded from nn_xyz.  A
+// frame that was not optimised has no records: type 0, neighbours NaN.
+__global__ void k_corr_gather(MapperDev D, int s, int nc, int nq, int optimize, int active0, int active1, int* type,
+                              double* rec, float* nbr) {
+  const size_t rb = (size_t)s * 2 * D.max_in;
+  for (int ridx = blockIdx.x * blockDim.x + threadIdx.x; ridx < nq; ridx += gridDim.x * blockDim.x) {
+    const int m = ridx < nc ? 0 : 1;
+    double* r = rec + (size_t)ridx * 10;
+    float* o = nbr + (size_t)ridx * 15;
+    const int t = optimize ? D.r_type[rb + ridx] : 0;
+    type[ridx] = t;
+    r[0] = (double)t;
+    r[1] = optimize ? (double)D.r_px[rb + ridx] : 0.0;
+    r[2] = optimize ? (double)D.r_py[rb + ridx] : 0.0;
+    r[3] = optimize ? (double)D.r_pz[rb + ridx] : 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      r[4 + k] = optimize ? D.r_a[k][rb + ridx] : 0.0;
+      r[7 + k] = optimize ? D.r_b[k][rb + ridx] : 0.0;
+    }
+    const bool has = optimize && D.knn_id[rb + ridx] >= 0;
+    const float4* lin = carena_base(D, s, m, m == 0 ? active0 : active1);
+    for (int j = 0; j < 5; ++j) {
+      float4 p = make_float4(NAN, NAN, NAN, 0.f);
+      if (has) p = D.sharded ? D.nn_xyz[j * D.knn_stride + rb + ridx] : lin[D.knn_id[j * D.knn_stride + rb + ridx]];
+      o[3 * j] = p.x;
+      o[3 * j + 1] = p.y;
+      o[3 * j + 2] = p.z;
+    }
   }
 }
 

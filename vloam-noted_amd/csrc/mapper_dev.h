@@ -73,6 +73,7 @@ struct StreamFrame {
   double wmap[7];
   int deferred;     // a queued frame found a recentering or compaction due: left to the host
   LmState lm[2];
+  double knn_pose[7];  // the pose the newest k_knn transformed its queries with (loam_mapper_corr_copy)
 };
 
 // per-stream input of a frame in the graph path (k_frame_prep), read from page-locked host

@@ -179,6 +179,44 @@ __global__ void k_knn_query(const float4* q, int nq, int k, float radius2, const
   }
 }
 
+// the line / plane fit of k_geom (mapper_corr.h) on given neighbour sets: edge_from_nbrs /
+// plane_from_nbrs of device_math.h and the record values k_geom derives from them
+__global__ void k_corr_geometry(const float* nbrs, int n, int which, int* ok, double* a, double* b) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    float nb[5][3];
+#pragma unroll
+    for (int j = 0; j < 5; ++j)
+#pragma unroll
+      for (int k = 0; k < 3; ++k) nb[j][k] = nbrs[(size_t)i * 15 + j * 3 + k];
+    double ra[3] = {0, 0, 0}, rb[3] = {0, 0, 0};
+    bool good;
+    if (which == 0) {
+      d3 pa, pb;
+      good = edge_from_nbrs(nb, pa, pb);
+      if (good) {
+        d3 de{pa.x - pb.x, pa.y - pb.y, pa.z - pb.z};
+        double dn = sqrt(de.x * de.x + de.y * de.y + de.z * de.z);
+        ra[0] = pa.x; ra[1] = pa.y; ra[2] = pa.z;
+        rb[0] = de.x / dn; rb[1] = de.y / dn; rb[2] = de.z / dn;
+      }
+    } else {
+      d3 nn;
+      double d;
+      good = plane_from_nbrs(nb, nn, d);
+      if (good) {
+        ra[0] = nn.x; ra[1] = nn.y; ra[2] = nn.z;
+        rb[0] = d;
+      }
+    }
+    ok[i] = good ? 1 : 0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      a[(size_t)i * 3 + k] = ra[k];
+      b[(size_t)i * 3 + k] = rb[k];
+    }
+  }
+}
+
 // host helpers: the untyped scratch of the one-shot entry points, zero-filled synchronously (their
 // kernels run on the null stream)
 using DevBytes = DevBuf<unsigned char>;
@@ -537,6 +575,31 @@ int32_t loam_voxel_merge(int32_t device, const float* fixed, int32_t n0, const f
   if (cnt) LOAM_HIP(hipMemcpy(out, (float4*)dout.p + off, sizeof(float4) * cnt, hipMemcpyDeviceToHost));
   *n_out = (int32_t)cnt;
   if (merged) *merged = m;
+  return LOAM_OK;
+}
+
+int32_t loam_corr_geometry(int32_t device, const float* nbrs, int32_t n, int32_t which, int32_t* ok, double* a,
+                           double* b) {
+  if (n < 0 || which < 0 || which > 1 || (n > 0 && (!nbrs || !ok || !a || !b))) {
+    set_error("loam_corr_geometry: bad arguments (which: 0 line, 1 plane)");
+    return LOAM_ERR_ARG;
+  }
+  int32_t rc = ensure_device(device);
+  if (rc != LOAM_OK) return rc;
+  LOAM_HIP(hipSetDevice(device));
+  if (n == 0) return LOAM_OK;
+  DevBytes dn, dok, da, db;
+  TRY(dmalloc<float>(dn, (size_t)n * 15));
+  TRY(dmalloc<int>(dok, n));
+  TRY(dmalloc<double>(da, (size_t)n * 3));
+  TRY(dmalloc<double>(db, (size_t)n * 3));
+  LOAM_HIP(hipMemcpy(dn.p, nbrs, sizeof(float) * 15 * n, hipMemcpyHostToDevice));
+  k_corr_geometry<<<std::min(1024, (n + 127) / 128), 128>>>((const float*)dn.p, n, which, (int*)dok.p, (double*)da.p,
+                                                           (double*)db.p);
+  LOAM_HIP(hipGetLastError());
+  LOAM_HIP(hipMemcpy(ok, dok.p, sizeof(int) * n, hipMemcpyDeviceToHost));
+  LOAM_HIP(hipMemcpy(a, da.p, sizeof(double) * 3 * n, hipMemcpyDeviceToHost));
+  LOAM_HIP(hipMemcpy(b, db.p, sizeof(double) * 3 * n, hipMemcpyDeviceToHost));
   return LOAM_OK;
 }
 

@@ -138,6 +138,7 @@ SIGNATURES = {
     "loam_mapper_cube_count": (c_i32, [vp, c_i32, c_i32, c_i32]),
     "loam_mapper_cube_copy": (c_i32, [vp, c_i32, c_i32, c_i32, vp]),
     "loam_mapper_stack_copy": (c_i32, [vp, c_i32, c_i32, vp, c_i32]),
+    "loam_mapper_corr_copy": (c_i32, [vp, c_i32, vp, vp, vp, vp, c_i32]),
     "loam_mapper_cube_set": (c_i32, [vp, c_i32, c_i32, c_i32, vp, c_i32]),
     "loam_mapper_map_copy": (c_i32, [vp, c_i32, vp, ctypes.c_int64]),
     "loam_mapper_register_cloud": (c_i32, [vp, c_i32, vp, c_i32, vp]),
@@ -182,6 +183,7 @@ SIGNATURES = {
     "loam_voxel_merge": (c_i32, [c_i32, vp, c_i32, vp, c_i32, c_f, vp, ctypes.POINTER(c_i32),
                                  ctypes.POINTER(c_i32)]),
     "loam_knn_radius": (c_i32, [c_i32, vp, c_i32, vp, c_i32, c_i32, c_f, vp, vp]),
+    "loam_corr_geometry": (c_i32, [c_i32, vp, c_i32, c_i32, vp, vp, vp]),
 }
 
 _LIB = None

@@ -107,6 +107,19 @@ class BatchMapper:
             check(lib().loam_mapper_stack_copy(self.h, stream, which, ptr(out), n))
         return out
 
+    def corr(self, stream=0):
+        """what the last solve's second outer round left for every query, corner stack first, then
+        surf stack (loam_mapper_corr_copy): x0 (7,) the pose the search started from, type (n,)
+        int32, records (n, 10) float64 (type, po, a, b), nbr (n, 5, 3) float32 (NaN: none)"""
+        x0 = np.empty(7)
+        n = check(lib().loam_mapper_corr_copy(self.h, stream, ptr(x0), None, None, None, 0))
+        typ = np.empty(n, dtype=np.int32)
+        rec = np.empty((n, 10))
+        nbr = np.empty((n, 5, 3), dtype=np.float32)
+        if n:
+            check(lib().loam_mapper_corr_copy(self.h, stream, ptr(x0), ptr(typ), ptr(rec), ptr(nbr), n))
+        return x0, typ, rec, nbr
+
     def lm_path(self):
         """the LM schedule of this handle: 0 two launches per iteration, 1 persistent round, 2 in-process
         group round, 3 persistent round with cross-process IPC peer slots (loam_mapper_lm_path)"""

@@ -62,6 +62,18 @@ def knn_radius(pts, queries, k=5, radius2=1.0, device=0):
     return idx, d2
 
 
+def corr_geometry(nbrs, which, device=0):
+    """the mapper's line (which 0) / plane (which 1) fit of (n, 5, 3) float32 neighbour sets in kNN
+    order: (ok (n,) bool, a (n, 3), b (n, 3)) as k_geom writes them into a factor record (line:
+    point_a, unit direction; plane: unit normal, b[:, 0] = negative_OA_dot_norm; zeros where not ok)"""
+    nb = np.ascontiguousarray(nbrs, dtype=np.float32).reshape(-1, 5, 3)
+    ok = np.empty(len(nb), dtype=np.int32)
+    a = np.empty((len(nb), 3))
+    b = np.empty((len(nb), 3))
+    check(lib().loam_corr_geometry(device, ptr(nb), len(nb), int(which), ptr(ok), ptr(a), ptr(b)))
+    return ok != 0, a, b
+
+
 def _factors(f):
     f = np.ascontiguousarray(f, dtype=np.float64)
     return f.reshape(-1, 10)
