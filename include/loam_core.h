@@ -321,8 +321,10 @@ int32_t loam_mapper_stats(loam_mapper* h, int32_t stream, loam_map_stats* st);
  * ([11..14] / [42..45] hold the rest), [66..67] cube sorts' depth-limit segments and their
  * elements, [68..69] the same for stack sorts, [91] the few-stream stack VoxelGrid's (k_stack_part)
  * histogram and range cuts ([42..45] then hold its bounding box, hash, sort + scan, member lists +
- * centroids, summed over its parts).
- * The cycle counters (all but [40], [41], [48], [49]; [52], [56], [66..69], [72], [77], [82..86], [90] count) run only in a handle created with the
+ * centroids, summed over its parts), [92] cell occupancy blocks in use now over the handle's
+ * (stream, map) pools (read from the pools' bitmaps; not reset), [93] cubes whose index was built
+ * without a block because the pool was exhausted (the 5-NN search probes every cell of such a cube).
+ * The cycle counters (all but [40], [41], [48], [49], [92], [93]; [52], [56], [66..69], [72], [77], [82..86], [90] count) run only in a handle created with the
  * environment variable LOAM_PHASE_COUNTERS=1 (they cost atomics in the kernels); else they stay 0. */
 #define LOAM_DEBUG_COUNTERS 96
 int32_t loam_mapper_debug_counters(loam_mapper* h, uint64_t* out, int32_t n, int32_t reset);

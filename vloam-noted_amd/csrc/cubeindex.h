@@ -24,6 +24,13 @@ namespace loam {
 constexpr uint32_t CI_EMPTY = 0xFFFFFFFFu;
 constexpr uint32_t CI_KEY_MASK = (1u << 18) - 1;
 constexpr int CI_LDS_MAX_T = 32768;  // table entries built in LDS (one packed word each)
+// Occupancy block of a cube (k_knn's empty-cell test): 51 x 51 words of 64 bits indexed [lz][ly], bit
+// lx set when cell (lx, ly, lz) holds a point (local coordinates 0..50, as in ci_local_key).  Built
+// with the table: one OR per cell, when the cell enters the table.
+constexpr int CI_OCC_DIM = 51;
+constexpr int CI_OCC_WORDS = 2602;  // 64-bit words of a block: 51 * 51 rounded up to 16 B
+constexpr int CI_OCC_LDS = 2 * CI_OCC_WORDS;  // the block's LDS image, after the table and the scan words
+constexpr int CI_OCC_LDS_AT = 32;             // (u32 words past the table; 16 B aligned)
 
 __host__ __device__ inline uint32_t ci_table_size(uint32_t n) {
   uint32_t t = 1;
@@ -66,22 +73,39 @@ __device__ inline uint32_t ci_block_scan(uint32_t v, uint32_t* ws, uint32_t* tot
   return r;
 }
 
+// bit of a cell key in a block: 32-bit word index (of the block's little-endian image) and bit; false: a
+// coordinate past 50, which no query asks for
+__device__ inline bool ci_occ_bit(uint32_t key, uint32_t* word, uint32_t* bit) {
+  const uint32_t lx = key & 63u, ly = (key >> 6) & 63u, lz = (key >> 12) & 63u;
+  *word = 2u * (lz * CI_OCC_DIM + ly) + (lx >> 5);
+  *bit = 1u << (lx & 31u);
+  return lx < (uint32_t)CI_OCC_DIM && ly < (uint32_t)CI_OCC_DIM && lz < (uint32_t)CI_OCC_DIM;
+}
+
 // Build the index of one cube (whole workgroup of nthreads, n points at pts).  lds: at least
-// CI_LDS_MAX_T + nthreads / 64 + 1 words.  Cubes with 2n > CI_LDS_MAX_T build their
-// table in global memory.  Returns false if a cell holds more points than the entry can
-// count (2^14 - 1).
+// MAXT + CI_OCC_LDS_AT + CI_OCC_LDS words.  Cubes with 2n > CI_LDS_MAX_T build their
+// table in global memory.  occ: the cube's occupancy block (null: none).  A block the cube already
+// owned (!occ_fresh) gets only the 16 B pieces that hold a bit now: a bit left over from a cell that has
+// emptied since costs the search one probe that finds nothing, and the pieces that hold nothing are most
+// of a block.  A block just taken from the pool is written whole.
+// Returns false if a cell holds more points than the entry can count (2^14 - 1).
 template <int nthreads, int MAXT = CI_LDS_MAX_T>
 __device__ inline bool cube_index_build(const float4* pts, uint32_t n, const int corner[3], float4* cpts,
-                                        uint2* ctab, uint32_t* lds, unsigned long long* prof = nullptr) {
+                                        uint2* ctab, uint32_t* lds, unsigned long long* prof = nullptr,
+                                        uint64_t* occ = nullptr, bool occ_fresh = true) {
+  static_assert(nthreads / 64 + 1 <= CI_OCC_LDS_AT && (MAXT + CI_OCC_LDS_AT) % 4 == 0, "block image after the scan words");
   const int tid = threadIdx.x;
   if (n == 0) return true;
   const uint32_t T = ci_table_size(n), mask = T - 1;
   uint32_t* ws = lds + MAXT;
+  uint32_t* locc = lds + MAXT + CI_OCC_LDS_AT;
   bool ok = true;
   if (prof && tid == 0 && T <= (uint32_t)MAXT && n < (1u << 14)) atomicAdd(prof, 0ull - __builtin_readcyclecounter());
   if (T <= (uint32_t)MAXT && n < (1u << 14)) {  // counts fit the packed word
     uint32_t* lent = lds;  // key | count << 18 (count < n <= 2^14)
     for (uint32_t i = tid; i < T; i += nthreads) lent[i] = CI_EMPTY;
+    if (occ)
+      for (uint32_t i = tid; i < (uint32_t)CI_OCC_LDS; i += nthreads) locc[i] = 0u;
     __syncthreads();
     // 1. cells + per-point rank, kept in registers (n <= MAXT / 2 here); the keys first, so
     //    every load is in flight before the first LDS atomic
@@ -118,7 +142,11 @@ __device__ inline bool cube_index_build(const float4* pts, uint32_t n, const int
         uint32_t h = ci_hash(key, mask);
         while (true) {
           const uint32_t old = atomicCAS(&lent[h], CI_EMPTY, key | (run << 18));
-          if (old == CI_EMPTY) break;
+          if (old == CI_EMPTY) {  // the cell's first points: its occupancy bit
+            uint32_t ow, ob;
+            if (occ && ci_occ_bit(key, &ow, &ob)) atomicOr(&locc[ow], ob);
+            break;
+          }
           if ((old & CI_KEY_MASK) == key) {
             base = atomicAdd(&lent[h], run << 18) >> 18;
             break;
@@ -132,6 +160,14 @@ __device__ inline bool cube_index_build(const float4* pts, uint32_t n, const int
     }
     __syncthreads();
     if (prof && tid == 0) atomicAdd(prof, __builtin_readcyclecounter());  // minus the start below
+    if (occ) {  // the block, 16 B per lane (nothing below waits for these stores)
+      const uint4* src = reinterpret_cast<const uint4*>(locc);
+      uint4* dst = reinterpret_cast<uint4*>(occ);
+      for (uint32_t i = tid; i < (uint32_t)CI_OCC_LDS / 4; i += nthreads) {
+        const uint4 v = src[i];
+        if (occ_fresh || (v.x | v.y | v.z | v.w)) dst[i] = v;
+      }
+    }
     // 2. starts: exclusive scan of the counts over the slots a thread owns (tid, tid + nthreads,
     //    ...: the cells' order in cpts is free, and the table writes coalesce); the LDS word
     //    becomes the start
@@ -166,12 +202,18 @@ __device__ inline bool cube_index_build(const float4* pts, uint32_t n, const int
   }
   // large cube: the same with the table in global memory (y = count, then start + fill)
   for (uint32_t i = tid; i < T; i += nthreads) ctab[i] = make_uint2(CI_EMPTY, 0);
+  if (occ && occ_fresh)
+    for (uint32_t i = tid; i < (uint32_t)CI_OCC_WORDS; i += nthreads) occ[i] = 0ull;
   __syncthreads();
   for (uint32_t i = tid; i < n; i += nthreads) {
     const uint32_t key = ci_local_key(pts[i], corner);
     uint32_t h = ci_hash(key, mask);
     while (true) {
       const uint32_t old = atomicCAS(&ctab[h].x, CI_EMPTY, key);
+      if (old == CI_EMPTY) {
+        uint32_t ow, ob;
+        if (occ && ci_occ_bit(key, &ow, &ob)) atomicOr(reinterpret_cast<uint32_t*>(occ) + ow, ob);
+      }
       if (old == CI_EMPTY || old == key) break;
       h = (h + 1) & mask;
     }

@@ -188,6 +188,7 @@ struct loam_mapper {
   uint2* cube_tab[2] = {nullptr, nullptr};
   int parity = 0;
   uint32_t* tok_tmp = nullptr;  // [B][2][NCUBE] the shifted fixed-point tokens
+  uint32_t* occ_tmp = nullptr;  // [B][2][NCUBE] the shifted occupancy block ids
   uint32_t* d_new_off = nullptr;
   DevPool pool;
   uint32_t frame_counter = 0;
@@ -569,6 +570,20 @@ static int32_t mapper_create(const loam_params* p, int32_t device, int32_t n_str
   TRY(alloc(D.ins_off, B * 2 * (size_t)(INS_SLOTS + 1)));
   TRY(alloc(D.stable_tok, B * 2 * (size_t)NCUBE));
   TRY(alloc(h->tok_tmp, B * 2 * (size_t)NCUBE));
+  {
+    // cell occupancy blocks: a pool of OCC_POOL per (stream, map) (sized from the window).  LOAM_KNN_OCC=0:
+    // no cube has a block, k_knn probes every cell (A/B runs, tests); LOAM_KNN_OCC_BLOCKS: a smaller
+    // pool (tests of the exhausted pool)
+    const char* oenv = std::getenv("LOAM_KNN_OCC");
+    const char* benv = std::getenv("LOAM_KNN_OCC_BLOCKS");
+    // handles of few streams search with the cell-split kernel, which does not read the blocks: none built
+    D.occ_blocks = (h->knn_cs || (oenv && oenv[0] == '0')) ? 0 : OCC_POOL;
+    if (D.occ_blocks && benv) D.occ_blocks = std::max(1, std::min(OCC_POOL, std::atoi(benv)));
+    TRY(alloc(D.cube_occ, B * 2 * (size_t)NCUBE));
+    TRY(alloc(h->occ_tmp, B * 2 * (size_t)NCUBE));
+    TRY(alloc(D.occ_used, B * 2 * (size_t)OCC_USED_WORDS));
+    TRY(alloc(D.occ_pool, B * 2 * (size_t)D.occ_blocks * CI_OCC_WORDS));
+  }
   TRY(alloc(D.dbg, LOAM_DEBUG_COUNTERS));
   {  // phase cycle counters (readcyclecounter + device-scope atomics in the kernels): diagnostics only
     const char* penv = std::getenv("LOAM_PHASE_COUNTERS");
@@ -712,6 +727,8 @@ int32_t loam_mapper_reset(loam_mapper* h) {
   for (int p = 0; p < 2; ++p)
     LOAM_HIP(hipMemsetAsync(h->cube_tab[p], 0, sizeof(uint2) * h->B * 2 * NCUBE, h->st));
   LOAM_HIP(hipMemsetAsync(h->D.stable_tok, 0, sizeof(uint32_t) * h->B * 2 * NCUBE, h->st));
+  LOAM_HIP(hipMemsetAsync(h->D.cube_occ, 0, sizeof(uint32_t) * h->B * 2 * NCUBE, h->st));
+  LOAM_HIP(hipMemsetAsync(h->D.occ_used, 0, sizeof(uint32_t) * h->B * 2 * OCC_USED_WORDS, h->st));
   LOAM_HIP(hipStreamSynchronize(h->st));
   for (int s = 0; s < h->B; ++s) {
     h->hf[s] = fresh_record();
@@ -1093,8 +1110,9 @@ static int32_t enqueue_frame(loam_mapper* h, bool chained, FrameRec& R) {
   // correspondences
   if (any_shift) {
     LAUNCH(FAM_OTHER, k_shift_cubes<<<dim3(16, B), 256, 0, st>>>(D, h->cube_tab[h->parity],
-                                                                 h->cube_tab[1 - h->parity], h->tok_tmp));
+                                                                 h->cube_tab[1 - h->parity], h->tok_tmp, h->occ_tmp));
     LOAM_HIP(hipMemcpyAsync(D.stable_tok, h->tok_tmp, sizeof(uint32_t) * B * 2 * NCUBE, hipMemcpyDeviceToDevice, st));
+    LOAM_HIP(hipMemcpyAsync(D.cube_occ, h->occ_tmp, sizeof(uint32_t) * B * 2 * NCUBE, hipMemcpyDeviceToDevice, st));
     h->parity ^= 1;
     D.cube_tab = h->cube_tab[h->parity];
   }
@@ -1568,6 +1586,12 @@ int32_t loam_mapper_debug_counters(loam_mapper* h, uint64_t* out, int32_t n, int
   LOAM_HIP(hipSetDevice(h->dev));
   LOAM_HIP(hipStreamSynchronize(h->st));
   LOAM_HIP(hipMemcpy(out, h->D.dbg, sizeof(uint64_t) * n, hipMemcpyDeviceToHost));
+  if (n > MD_OCC_IN_USE) {  // occupancy blocks taken now, over the handle's (stream, map) pools
+    std::vector<uint32_t> used((size_t)h->B * 2 * OCC_USED_WORDS);
+    LOAM_HIP(hipMemcpy(used.data(), h->D.occ_used, sizeof(uint32_t) * used.size(), hipMemcpyDeviceToHost));
+    out[MD_OCC_IN_USE] = 0;
+    for (uint32_t w : used) out[MD_OCC_IN_USE] += (uint64_t)__builtin_popcount(w);
+  }
   if (reset) LOAM_HIP(hipMemset(h->D.dbg, 0, sizeof(uint64_t) * LOAM_DEBUG_COUNTERS));
   return LOAM_OK;
 }

@@ -59,6 +59,9 @@ template <int L, bool CS = false>
 __global__ void __launch_bounds__(CORR_THREADS) __attribute__((amdgpu_waves_per_eu(CS ? 4 : KNN_WAVES, 8))) k_knn(MapperDev D, int round) {
   __shared__ WinMap W[2];
   __shared__ int slot_of[75];  // 5 x 5 x 3 window position -> slot (laserCloudValidInd order)
+  // window position -> the cube's occupancy block id + 1, OCC_NONE: it has none, OCC_ABSENT: no such
+  // cube in the submap, or nothing in it
+  __shared__ uint32_t wocc[2][75];
   int s, blk;
   corr_block(D, &s, &blk);
   StreamFrame& F = D.fr[s];
@@ -76,6 +79,7 @@ __global__ void __launch_bounds__(CORR_THREADS) __attribute__((amdgpu_waves_per_
   const int tid = threadIdx.x;
   const int c0 = F.center[0] - 2, c1 = F.center[1] - 2, c2 = F.center[2] - 1;
   if (tid < 75) slot_of[tid] = -1;
+  if (L == 1 && !CS && tid < 75) wocc[0][tid] = wocc[1][tid] = OCC_ABSENT;  // (the cell-split kernel does not read it)
   __syncthreads();
   if (tid < F.valid_num) {
     const int cube = F.window[tid];
@@ -84,6 +88,7 @@ __global__ void __launch_bounds__(CORR_THREADS) __attribute__((amdgpu_waves_per_
 #pragma unroll
     for (int m = 0; m < 2; ++m) {
       const uint2 cv = D.cube_tab[sm_index(s, m) * NCUBE + cube];
+      if (L == 1 && !CS && cv.y) wocc[m][(ci - c0) * 15 + (cj - c1) * 3 + (ck - c2)] = D.cube_occ[sm_index(s, m) * NCUBE + cube];
       W[m].off[tid] = cv.x;
       W[m].n[tid] = cv.y;
       W[m].tsize[tid] = cv.y ? ci_table_size(cv.y) : 0u;
@@ -137,17 +142,8 @@ __global__ void __launch_bounds__(CORR_THREADS) __attribute__((amdgpu_waves_per_
         near5_offer(T, fdist2(q.x, q.y, q.z, p.x, p.y, p.z), key, (int)pos);
       }
     };
-    for (int ob = 0; ob < 27; ob += CS ? L : 1) {
-      const int o = CS ? ob + gsub : ob;
-      const uint32_t code = cell_order_code(o < 27 ? o : 0);
-      const int dx = (int)(code & 3u) - 1, dy = (int)((code >> 2) & 3u) - 1, dz = (int)(code >> 4) - 1;
-      const float gx = dx < 0 ? lx : (dx > 0 ? hx : 0.f);
-      const float gy = dy < 0 ? ly : (dy > 0 ? hy : 0.f);
-      const float gz = dz < 0 ? lz : (dz > 0 ? hz : 0.f);
-      float bound = fminf(T.d[4], 1.0f) * 1.01f + 1e-6f;  // rounding margin
-#pragma unroll
-      for (int o2 = 1; o2 < L; o2 <<= 1) bound = fminf(bound, __shfl_xor(bound, o2, 64));
-      if (o >= 27 || gx * gx + gy * gy + gz * gz > bound) continue;
+    // cell (qx + dx, qy + dy, qz + dz): its cube and local coordinates, and the cubes below at an edge
+    auto visit = [&](int dx, int dy, int dz) {
       const int x = qx + dx, y = qy + dy, z = qz + dz;
       const int bi = floor_div50(x + 25) + F.cen[0], bj = floor_div50(y + 25) + F.cen[1],
                 bk = floor_div50(z + 25) + F.cen[2];
@@ -171,6 +167,120 @@ __global__ void __launch_bounds__(CORR_THREADS) __attribute__((amdgpu_waves_per_
           l2[a] = (e >> a) & 1 ? 50 : lc[a];
         }
         scan(b2[0], b2[1], b2[2], l2[0], l2[1], l2[2]);
+      }
+    };
+    if constexpr (L == 1 && !CS) {
+      // One lane per query: the lane's own occupied cells only.  Bit o of `cells` (nearest-first order,
+      // cell_order_code) is clear where the cell is known to be empty: its cube is not in the submap,
+      // holds nothing, or the cube's occupancy block (cubeindex.h) has the cell's bit clear.  A cell
+      // the block does not decide keeps its bit and is probed as before: a cube without a block, a
+      // cell in another cube along x than the query's, a coordinate with the edge rule below.  Empty
+      // cells offer nothing and count nothing, so the result and `cand` are those of all 27 cells.
+      uint32_t cells = 0x7FFFFFFu;
+      if (D.occ_blocks) {
+        const uint64_t* pool = D.occ_pool + sm_index(s, m) * D.occ_blocks * (size_t)CI_OCC_WORDS;
+        const uint32_t* wo = wocc[m];
+        const int qv[3] = {qx, qy, qz};
+        int wb[3][3], lo[3][3];  // [axis][offset + 1]: window coordinate of the cube, local coordinate
+        uint32_t open[3] = {0u, 0u, 0u};  // per axis, bit offset + 1: the block does not decide
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+#pragma unroll
+          for (int d = 0; d < 3; ++d) {
+            const int v = qv[a] + d - 1;
+            const int bc = floor_div50(v + 25) + F.cen[a];
+            wb[a][d] = bc - (a == 0 ? c0 : (a == 1 ? c1 : c2));
+            lo[a][d] = v - ci_corner(bc, F.cen[a]);
+            if (v + 25 < 0 && (v + 25) % 50 == 0) open[a] |= 1u << d;
+          }
+        }
+        if (wb[0][0] != wb[0][1]) open[0] |= 1u;
+        if (wb[0][2] != wb[0][1]) open[0] |= 4u;
+        // the nine (y, z) rows of the query's x cube, every load issued before the first is used
+        uint64_t row[9];
+#pragma unroll
+        for (int r = 0; r < 9; ++r) {
+          const int dy = r % 3, dz = r / 3;
+          const int wx = wb[0][1], wy = wb[1][dy], wz = wb[2][dz];
+          const bool in = wx >= 0 && wx <= 4 && wy >= 0 && wy <= 4 && wz >= 0 && wz <= 2;
+          const uint32_t id = in ? wo[wx * 15 + wy * 3 + wz] : OCC_ABSENT;
+          const bool has = id != OCC_ABSENT && id != OCC_NONE;
+          const uint64_t w = pool[has ? (size_t)(id - 1) * CI_OCC_WORDS + (size_t)(lo[2][dz] * CI_OCC_DIM + lo[1][dy]) : 0];
+          row[r] = has ? w : (id == OCC_ABSENT ? 0ull : ~0ull);
+          if ((open[1] >> dy | open[2] >> dz) & 1u) row[r] = ~0ull;
+        }
+        // (lo[0][1] - 1 is -1 only where open[0] has bit 0, lo[0][1] + 1 is 50 only where it has bit 2)
+        const int sh = lo[0][1] > 0 ? lo[0][1] - 1 : 0;
+        const int up = lo[0][1] > 0 ? 0 : 1;
+        cells = 0u;
+#pragma unroll
+        for (int o = 0; o < 27; ++o) {
+          const uint32_t code = cell_order_code(o);
+          const int dx = (int)(code & 3u), dy = (int)((code >> 2) & 3u), dz = (int)(code >> 4);
+          const uint32_t t3 = ((uint32_t)(row[dz * 3 + dy] >> sh) << up) | open[0];
+          cells |= ((t3 >> dx) & 1u) << o;
+        }
+      }
+      // Two loops, not one `while (cells)`: the inner one is arithmetic only and skips the cells the bound
+      // prunes, so that every lane that still has an admitted cell arrives at `visit` (the memory chain) in
+      // the same trip of the outer loop; with the gap test and a `continue` in one loop, a lane whose cell is
+      // pruned would idle through the other lanes' probe.
+      while (true) {
+        // the lane's next occupied cell the bound admits (the same test, in the same order, as below)
+        const float bound = fminf(T.d[4], 1.0f) * 1.01f + 1e-6f;  // rounding margin
+        int dx = 0, dy = 0, dz = 0;
+        bool found = false;
+        while (cells && !found) {
+          const int o = __builtin_ctz(cells);
+          cells &= cells - 1u;
+          const uint32_t code = cell_order_code(o);
+          dx = (int)(code & 3u) - 1, dy = (int)((code >> 2) & 3u) - 1, dz = (int)(code >> 4) - 1;
+          const float gx = dx < 0 ? lx : (dx > 0 ? hx : 0.f);
+          const float gy = dy < 0 ? ly : (dy > 0 ? hy : 0.f);
+          const float gz = dz < 0 ? lz : (dz > 0 ? hz : 0.f);
+          found = !(gx * gx + gy * gy + gz * gz > bound);
+        }
+        if (!found) break;
+        visit(dx, dy, dz);
+      }
+    } else {
+      // (the cell's visit is written out here, not a call of `visit`: through the lambda this instantiation
+      // took 97 VGPRs instead of 95, a wave per SIMD less)
+      for (int ob = 0; ob < 27; ob += CS ? L : 1) {
+        const int o = CS ? ob + gsub : ob;
+        const uint32_t code = cell_order_code(o < 27 ? o : 0);
+        const int dx = (int)(code & 3u) - 1, dy = (int)((code >> 2) & 3u) - 1, dz = (int)(code >> 4) - 1;
+        const float gx = dx < 0 ? lx : (dx > 0 ? hx : 0.f);
+        const float gy = dy < 0 ? ly : (dy > 0 ? hy : 0.f);
+        const float gz = dz < 0 ? lz : (dz > 0 ? hz : 0.f);
+        float bound = fminf(T.d[4], 1.0f) * 1.01f + 1e-6f;  // rounding margin
+#pragma unroll
+        for (int o2 = 1; o2 < L; o2 <<= 1) bound = fminf(bound, __shfl_xor(bound, o2, 64));
+        if (o >= 27 || gx * gx + gy * gy + gz * gz > bound) continue;
+        const int x = qx + dx, y = qy + dy, z = qz + dz;
+        const int bi = floor_div50(x + 25) + F.cen[0], bj = floor_div50(y + 25) + F.cen[1],
+                  bk = floor_div50(z + 25) + F.cen[2];
+        int cx[3] = {bi, bj, bk};
+        int lc[3];
+        const int cv[3] = {x, y, z};
+  #pragma unroll
+        for (int a = 0; a < 3; ++a) lc[a] = cv[a] - ci_corner(cx[a], F.cen[a]);
+        scan(bi, bj, bk, lc[0], lc[1], lc[2]);
+        // the reference files points at an exact negative multiple of 50 (v + 25) in the cube
+        // below (laser_mapping.cpp:747-756): local coordinate 50 there
+        int edge = 0;
+  #pragma unroll
+        for (int a = 0; a < 3; ++a)
+          if (cv[a] + 25 < 0 && (cv[a] + 25) % 50 == 0) edge |= 1 << a;
+        for (int e = edge; e; e = (e - 1) & edge) {
+          int b2[3], l2[3];
+  #pragma unroll
+          for (int a = 0; a < 3; ++a) {
+            b2[a] = (e >> a) & 1 ? cx[a] - 1 : cx[a];
+            l2[a] = (e >> a) & 1 ? 50 : lc[a];
+          }
+          scan(b2[0], b2[1], b2[2], l2[0], l2[1], l2[2]);
+        }
       }
     }
 #pragma unroll

@@ -32,8 +32,15 @@ enum MapDbg {
   MD_CUBE_HOT = 50, MD_STACK_HOT = 54, MD_PREP_CYC = 58 /* [4]: FrameIn load, preparation, stack sizes, submap */,
   MD_PREP_LAUNCHES = 62, MD_PREP_ON_DEVICE = 63, MD_CUBE_GLOB = 64, MD_STACK_GLOB = 65, MD_CUBE_HEAP = 66 /* [2] */,
   MD_STACK_HEAP = 68 /* [2] */, MD_CUBE_SORT = 72, MD_STACK_SORT = 77, MD_CUBE_WAVES = 82, MD_STACK_CUTS = 91,
-  MD_DBG_END = 92
+  MD_OCC_IN_USE = 92 /* filled by the host from occ_used */, MD_OCC_ALLOC_FAIL = 93,
+  MD_DBG_END = 94
 };
+// occupancy blocks (cubeindex.h) of a (stream, map): the window's cubes plus a margin for cubes
+// outside the window that hold content; one bit per block in occ_used
+constexpr int OCC_POOL = 160, OCC_USED_WORDS = OCC_POOL / 32;
+static_assert(OCC_POOL >= WIN_MAX && OCC_POOL % 32 == 0, "occupancy pool");
+// k_knn's window view of cube_occ: the cube is not in the submap or empty / has no block
+constexpr uint32_t OCC_ABSENT = 0xFFFFFFFFu, OCC_NONE = 0u;
 static_assert(MD_POSE_DIFF == 40 && MD_COMPACTIONS == 41 && MD_COMPACTIONS_MAP + 1 == 49, "slots the tests read by number");
 static_assert(MD_CUBE_HOT + VHF_SLOTS <= MD_STACK_HOT && MD_STACK_HOT + VHF_SLOTS <= MD_PREP_CYC &&
                   MD_CUBE_SORT + VHS_SLOTS == MD_STACK_SORT && MD_STACK_SORT + VHS_SLOTS == MD_CUBE_WAVES &&
@@ -118,7 +125,14 @@ struct MapperDev {
   uint2* ctab;    // [B][2 maps][2 arenas][4 * map_cap]: each cube's cell table
   uint2* cube_tab;  // [B][2 maps][NCUBE] (off, cnt) — current parity
   uint32_t* extra_flag;  // [B][2][NCUBE]
-  int* knn_id;      // [5][B][2*max_in] neighbour ids (submap index) per query, -1: none
+  // cell occupancy (k_knn skips empty cells): a cube's block id + 1 in its (stream, map)'s pool, 0: none
+  // (pool exhausted: every cell "maybe occupied").  Indexed by cube, not by arena offset: a compaction
+  // leaves it alone, a window shift moves the id (k_shift_cubes).
+  uint32_t* cube_occ;   // [B][2][NCUBE]
+  uint32_t* occ_used;   // [B][2][OCC_USED_WORDS] blocks taken
+  uint64_t* occ_pool;   // [B][2][occ_blocks][CI_OCC_WORDS]
+  int occ_blocks = 0;   // blocks per (stream, map); 0: off (LOAM_KNN_OCC=0), k_knn probes every cell
+  int* knn_id;     // [5][B][2*max_in] neighbour ids (submap index) per query, -1: none
   size_t knn_stride;
   // factor records (SoA) [B][2*max_in]
   int* r_type;
@@ -219,13 +233,58 @@ __device__ inline void cube_corner(int c, const int* cen, int corner[3]) {
   corner[2] = ci_corner(c / (CW * CH), cen[2]);
 }
 
+// occupancy block `id` (1-based) of pair sm
+__device__ inline uint64_t* occ_block(const MapperDev& D, size_t sm, uint32_t id) {
+  return D.occ_pool + (sm * D.occ_blocks + (id - 1)) * (size_t)CI_OCC_WORDS;
+}
+__device__ inline void occ_release(const MapperDev& D, size_t sm, uint32_t id) {
+  atomicAnd(&D.occ_used[sm * OCC_USED_WORDS + (id - 1) / 32], ~(1u << ((id - 1) & 31)));
+}
+// a free block of pair sm (any thread; takers and releasers may run side by side); 0: none left
+__device__ inline uint32_t occ_alloc(const MapperDev& D, size_t sm) {
+  uint32_t* used = D.occ_used + sm * OCC_USED_WORDS;
+  for (int w = 0; 32 * w < D.occ_blocks; ++w) {
+    const int nb = D.occ_blocks - 32 * w;
+    const uint32_t valid = nb >= 32 ? 0xFFFFFFFFu : (1u << nb) - 1u;
+    uint32_t cur = atomicOr(&used[w], 0u);
+    while (~cur & valid) {
+      const int b = __ffs((int)(~cur & valid)) - 1;
+      cur = atomicOr(&used[w], 1u << b);
+      if (!((cur >> b) & 1u)) return (uint32_t)(32 * w + b + 1);  // the bit was clear: taken
+    }
+  }
+  return 0;
+}
+// The block the index build of (sm, cube) with n points writes (one thread per cube): the cube's own, else
+// a free one (OCC_FRESH set: its old content is another cube's); an empty cube gives its block back.  0: none.
+constexpr uint32_t OCC_FRESH = 0x80000000u;
+__device__ inline uint32_t occ_acquire(const MapperDev& D, size_t sm, int cube, uint32_t n) {
+  if (!D.occ_blocks) return 0;
+  uint32_t* slot = D.cube_occ + sm * NCUBE + cube;
+  uint32_t id = *slot;
+  if (n == 0) {
+    if (id) {
+      occ_release(D, sm, id);
+      *slot = 0;
+    }
+    return 0;
+  }
+  if (id) return id;
+  id = occ_alloc(D, sm);
+  if (id) *slot = id;
+  else atomicAdd(&D.dbg[MD_OCC_ALLOC_FAIL], 1ull);
+  return id ? id | OCC_FRESH : 0u;
+}
+
 // ---------------------------------------------------------------------------------------
 // ring-buffer recentering (laser_mapping.cpp:252-444): content moves by shift[axis] cube
 // indices, the slabs that wrap around are cleared.
 // ---------------------------------------------------------------------------------------
 // The fixed-point tokens move with their cubes (into tok_tmp, copied back on the same stream):
-// a token left at the old index would send every moved cube through a full re-filter.
-__global__ void k_shift_cubes(MapperDev D, const uint2* __restrict__ old_tab, uint2* new_tab, uint32_t* tok_tmp) {
+// a token left at the old index would send every moved cube through a full re-filter.  So do the
+// occupancy block ids (occ_tmp); a cube that leaves the grid gives its block back.
+__global__ void k_shift_cubes(MapperDev D, const uint2* __restrict__ old_tab, uint2* new_tab, uint32_t* tok_tmp,
+                              uint32_t* occ_tmp) {
   int s = D.s0 + blockIdx.y;
   const StreamFrame& F = D.fr[s];
   for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < 2 * NCUBE; t += gridDim.x * blockDim.x) {
@@ -233,14 +292,20 @@ __global__ void k_shift_cubes(MapperDev D, const uint2* __restrict__ old_tab, ui
     int i = c % CW, j = (c / CW) % CH, k = c / (CW * CH);
     int oi = i - F.shift[0], oj = j - F.shift[1], ok = k - F.shift[2];
     uint2 v = make_uint2(0, 0);
-    uint32_t tok = 0;
+    uint32_t tok = 0, occ = 0;
     if (oi >= 0 && oi < CW && oj >= 0 && oj < CH && ok >= 0 && ok < CD) {
       const size_t o = sm_index(s, m) * NCUBE + oi + CW * oj + CW * CH * ok;
       v = old_tab[o];
       tok = D.stable_tok[o];
+      occ = D.cube_occ[o];
     }
     new_tab[sm_index(s, m) * NCUBE + c] = v;
     tok_tmp[sm_index(s, m) * NCUBE + c] = tok;
+    occ_tmp[sm_index(s, m) * NCUBE + c] = occ;
+    // cube c of the old grid: where it goes
+    const int ni = i + F.shift[0], nj = j + F.shift[1], nk = k + F.shift[2];
+    const uint32_t mine = D.cube_occ[sm_index(s, m) * NCUBE + c];
+    if (mine && (ni < 0 || ni >= CW || nj < 0 || nj >= CH || nk < 0 || nk >= CD)) occ_release(D, sm_index(s, m), mine);
   }
 }
 

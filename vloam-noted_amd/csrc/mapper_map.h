@@ -228,6 +228,8 @@ __device__ inline void revox_item(MapperDev& D, int s, int m, int slot, int cube
   uint32_t* tok = D.stable_tok + sm_index(s, m) * NCUBE + cube;
   uint2* tab = D.cube_tab + sm_index(s, m) * NCUBE;
   const uint2 cv = tab[cube];
+  // the cube's occupancy block, loaded here so that the index build below does not wait for it
+  const uint32_t occ0 = D.occ_blocks ? D.cube_occ[sm_index(s, m) * NCUBE + cube] : 0u;
   if (cv.y + n_new < (uint32_t)REVOX_PROF_MIN_N) D.pdbg = nullptr;
   float4* ar = arena_base(D, s, m, F.arena_active[m]);
   VoxSeg S;
@@ -279,18 +281,21 @@ __device__ inline void revox_item(MapperDev& D, int s, int m, int slot, int cube
   const unsigned long long t1 = __builtin_readcyclecounter();
   // the cube's new content -> its cell index (cubeindex.h)
   uint32_t* res = vx_park_result(lds);
+  uint32_t* occ_id = vx_park_block(lds);  // (the sort scratch block is done with)
   if (threadIdx.x == 0) {
     const uint2 v = tab[cube];  // written by this thread inside the filter
     res[0] = v.x;
     res[1] = v.y;
+    *occ_id = (occ0 && v.y) ? occ0 : occ_acquire(D, sm_index(s, m), cube, v.y);
   }
   __syncthreads();
-  const uint32_t off = res[0], n = res[1];
+  const uint32_t off = res[0], n = res[1], oid = *occ_id;
   __syncthreads();  // res may lie in the index build's LDS
   int corner[3];
   cube_corner(cube, F.cen, corner);
   if (!cube_index_build<VX_THREADS, CI_LDS_MAX_T>(ar + off, n, corner, carena_base(D, s, m, F.arena_active[m]) + off,
-                                  ctab_base(D, s, m, F.arena_active[m]) + 4 * (size_t)off, lds, D.pdbg ? D.pdbg + MD_INDEX_HASH_CYC : nullptr) &&
+                                  ctab_base(D, s, m, F.arena_active[m]) + 4 * (size_t)off, lds, D.pdbg ? D.pdbg + MD_INDEX_HASH_CYC : nullptr,
+                                  oid ? occ_block(D, sm_index(s, m), oid & ~OCC_FRESH) : nullptr, (oid & OCC_FRESH) != 0) &&
       threadIdx.x == 0)
     atomicOr(&F.err, MAP_ERR_INDEX);
   // read old content + new points, write the filtered cube, then its index (read it, write
@@ -321,6 +326,7 @@ __device__ inline void revox_item(MapperDev& D, int s, int m, int slot, int cube
 // class first, so the longest items are dispatched first; workgroups past the list's end leave
 // after one load.  PCL: exact_voxel_order (its own instantiation, so that the sort's registers do
 // not weigh on the input-order kernel)
+static_assert(CI_LDS_MAX_T + CI_OCC_LDS_AT + CI_OCC_LDS <= VX_LDS_WORDS - VX_TAIL_WORDS, "index build LDS");
 template <bool PCL>
 __global__ void __launch_bounds__(VX_THREADS) k_revox(MapperDev D) {
   __shared__ __attribute__((aligned(16))) uint32_t lds[VX_LDS_WORDS];
@@ -344,11 +350,14 @@ __global__ void __launch_bounds__(VX_THREADS) k_revox(MapperDev D) {
 // cell index of one cube whose content was set through the API (cen: the host's grid centre)
 __global__ void __launch_bounds__(VX_THREADS) k_cube_index(MapperDev D, int s, int m, int c0, int c1,
                                                            int3 cen) {
-  __shared__ __attribute__((aligned(16))) uint32_t lds[CI_LDS_MAX_T + VX_WAVES + 1];
+  __shared__ __attribute__((aligned(16))) uint32_t lds[CI_LDS_MAX_T + CI_OCC_LDS_AT + CI_OCC_LDS];
+  __shared__ uint32_t occ_id;
   const int cube = c0 + blockIdx.x;
   if (cube >= c1) return;
   StreamFrame& F = D.fr[s];
   const uint2 cv = D.cube_tab[sm_index(s, m) * NCUBE + cube];
+  if (threadIdx.x == 0) occ_id = occ_acquire(D, sm_index(s, m), cube, cv.y);  // (an emptied cube's block goes back)
+  __syncthreads();
   if (cv.y == 0) return;
   const int cenv[3] = {cen.x, cen.y, cen.z};
   int corner[3];
@@ -356,7 +365,8 @@ __global__ void __launch_bounds__(VX_THREADS) k_cube_index(MapperDev D, int s, i
   const int active = F.arena_active[m];
   if (!cube_index_build<VX_THREADS>(arena_base(D, s, m, active) + cv.x, cv.y, corner,
                                     carena_base(D, s, m, active) + cv.x,
-                                    ctab_base(D, s, m, active) + 4 * (size_t)cv.x, lds) &&
+                                    ctab_base(D, s, m, active) + 4 * (size_t)cv.x, lds, nullptr,
+                                    occ_id ? occ_block(D, sm_index(s, m), occ_id & ~OCC_FRESH) : nullptr, (occ_id & OCC_FRESH) != 0) &&
       threadIdx.x == 0)
     atomicOr(&F.err, MAP_ERR_INDEX);
 }
