@@ -519,7 +519,10 @@ int32_t loam_vo_solve(int32_t device, int32_t n_problems, const int32_t* offsets
  * pairs per handle and call: ImageUtil::matchDescriptors (image_util.cpp:347-438: BFMatcher
  * NORM_HAMMING, knnMatch k = 2, ratio test), the outlier gate (:363-368), queryDepth of the
  * previous point (:371), the CostFunctor32 / CostFunctor22 records (:400-474) and the solve, as
- * one launch sequence.  Keypoint detection and ORB description stay with OpenCV.
+ * one launch sequence.  optical_flow_match = true: either the LK tracks, or the two images and
+ * the points to track (loam_vo_frames_input_images below: the cv::calcOpticalFlowPyrLK call of
+ * ImageUtil::calculateOpticalFlow runs on the device in front of the rest).  Keypoint detection
+ * (ORB, or goodFeaturesToTrack for the optical-flow mode) and ORB description stay with OpenCV.
  * ------------------------------------------------------------------------------------ */
 typedef struct loam_vo_frames loam_vo_frames;
 typedef struct loam_vo_frames_params {
@@ -572,6 +575,44 @@ int32_t loam_vo_frames_result(loam_vo_frames* h, int32_t pair, double* x6, loam_
 int32_t loam_vo_frames_matches_copy(loam_vo_frames* h, int32_t pair, int32_t* out, int32_t cap);
 int32_t loam_vo_frames_records_copy(loam_vo_frames* h, int32_t pair, double* records, float* depth0,
                                     int32_t cap);
+
+/* optical_flow_match = true from the images: cv::calcOpticalFlowPyrLK (OpenCV 4.2, 8-bit single
+ * channel, flags 0: no initial flow, no minimum-eigenvalue output) as ImageUtil::
+ * calculateOpticalFlow calls it (image_util.cpp:503-570).  The sums over the window are exact
+ * integers (OpenCV adds floats in an order its SIMD width decides); everything else follows
+ * OpenCV operation by operation. */
+typedef struct loam_lk_params {
+  int32_t max_width, max_height;  /* largest image; no default (0) */
+  int32_t win;                    /* 15: winSize (square, odd, 3..31) */
+  int32_t max_level;              /* 2: maxLevel, 0..7; fewer levels where one would be <= win */
+  int32_t max_count;              /* 10: criteria.maxCount, clamped to 0..100 */
+  double  epsilon;                /* 0.03: criteria.epsilon, clamped to 0..10 */
+  double  min_eig_threshold;      /* 1e-4: minEigThreshold */
+} loam_lk_params;
+void    loam_lk_params_default(loam_lk_params* p);
+/* allocates the image pyramids of every pair (once per handle).  LOAM_ERR_ARG: win not odd in
+ * 3..31, a size <= 0 or max_level outside 0..7; LOAM_ERR_CAPACITY: more than 2 GiB of pyramids
+ * or more than 32767 pairs; LOAM_ERR_STATE: already enabled */
+int32_t loam_vo_frames_enable_images(loam_vo_frames* h, const loam_lk_params* p);
+/* previous and current image (8-bit, height rows of width pixels, row_stride bytes apart) and
+ * the n points (2 floats each) of the previous image to track; host memory, copied.  The solve
+ * tracks them (status 1 = tracked) and goes on as if loam_vo_frames_input_tracks had been given
+ * pts_xy, the tracked points and the status.  LOAM_ERR_STATE before loam_vo_frames_enable_images;
+ * LOAM_ERR_CAPACITY: an image over the maximum or n over max_keypoints */
+int32_t loam_vo_frames_input_images(loam_vo_frames* h, int32_t pair, const uint8_t* img_prev,
+                                    const uint8_t* img_curr, int32_t width, int32_t height, int32_t row_stride,
+                                    const float* pts_xy, int32_t n, int32_t depth_stream_prev);
+/* for parity tests and the node's flow visualisation: the tracks of the pair's last solve
+ * (tracks and images pairs; err is LK's and 0 for a tracks pair); each pointer may be NULL; copy
+ * when cap >= count; return count.  LOAM_ERR_STATE: never solved, solved from descriptors, or a
+ * later input has replaced the points */
+int32_t loam_vo_frames_tracks_copy(loam_vo_frames* h, int32_t pair, float* prev_xy, float* curr_xy,
+                                   uint8_t* status, float* err, int32_t cap);
+/* for parity tests: one pyramid level of the pair's last images solve (image 0 previous /
+ * 1 current), dense rows; wh (may be NULL) gets its width and height; copy when cap >= width *
+ * height; return width * height.  LOAM_ERR_ARG: a level the pair does not have */
+int32_t loam_vo_frames_pyramid_copy(loam_vo_frames* h, int32_t pair, int32_t image, int32_t level, uint8_t* out,
+                                    int32_t cap, int32_t* wh);
 
 /* --------------------------------------------------------------------------------------
  * Device LM engine on an explicit factor list (lidarFactor.hpp + Ceres TR-LM).  Factor

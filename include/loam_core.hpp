@@ -238,6 +238,14 @@ class LaserMapping {
   BatchMapper m_;
 };
 
+inline loam_lk_params default_lk_params(int32_t max_width, int32_t max_height) {
+  loam_lk_params p;
+  loam_lk_params_default(&p);
+  p.max_width = max_width;
+  p.max_height = max_height;
+  return p;
+}
+
 inline loam_vo_frames_params default_vo_frames_params() {
   loam_vo_frames_params p;
   loam_vo_frames_params_default(&p);
@@ -245,13 +253,19 @@ inline loam_vo_frames_params default_vo_frames_params() {
 }
 
 // VisualOdometry::solveNlsAll with the matcher in front of it (visual_odometry.cpp:304-509,
-// image_util.cpp:347-438), n_pairs frame pairs per call: descriptors or LK tracks in,
-// angles_0to1 / t_0to1 out.  `depth` is the loam_depth handle whose streams hold the previous
+// image_util.cpp:347-438), n_pairs frame pairs per call: descriptors, LK tracks, or the two images
+// and the points to track (ImageUtil::calculateOpticalFlow's cv::calcOpticalFlowPyrLK on the device)
+// in, angles_0to1 / t_0to1 out.  `depth` is the loam_depth handle whose streams hold the previous
 // frames' buckets (point_cloud_utils[1 - i]); it must outlive this object.
 class VisualOdometryFrames {
  public:
   struct Match {  // cv::DMatch's fields
     int32_t queryIdx, trainIdx, distance;
+  };
+  struct Tracks {  // calcOpticalFlowPyrLK's prevPts, nextPts (x, y interleaved), status, err
+    std::vector<float> prev_xy, curr_xy;
+    std::vector<uint8_t> status;
+    std::vector<float> err;
   };
 
   VisualOdometryFrames(const loam_vo_frames_params& p, loam_depth* depth, int32_t n_pairs = 1) {
@@ -272,6 +286,15 @@ class VisualOdometryFrames {
                    int32_t depth_stream_prev) {
     check(loam_vo_frames_input_tracks(h_, pair, prev_xy, curr_xy, status, n, depth_stream_prev));
   }
+  // once, before inputImages: the pyramids of every pair
+  void enableImages(const loam_lk_params& p) { check(loam_vo_frames_enable_images(h_, &p)); }
+  // optical_flow_match from the images themselves: 8-bit rows row_stride bytes apart, and the n
+  // points of img_prev to track
+  void inputImages(int32_t pair, const uint8_t* img_prev, const uint8_t* img_curr, int32_t width, int32_t height,
+                   int32_t row_stride, const float* pts_xy, int32_t n, int32_t depth_stream_prev) {
+    check(loam_vo_frames_input_images(h_, pair, img_prev, img_curr, width, height, row_stride, pts_xy, n,
+                                      depth_stream_prev));
+  }
   // angles_0to1 ++ t_0to1 the solves start from; nullptr: zeros (reset_VO_to_identity)
   void setInitial(int32_t pair, const double* x6 = nullptr) { check(loam_vo_frames_set_initial(h_, pair, x6)); }
   void solveNlsAll() { check(loam_vo_frames_solve(h_)); }
@@ -288,6 +311,18 @@ class VisualOdometryFrames {
     std::vector<Match> out(static_cast<size_t>(n));
     if (n) check(loam_vo_frames_matches_copy(h_, pair, &out[0].queryIdx, n));
     return out;
+  }
+  // the tracks of the pair's last tracks / images solve (for the flow visualisation)
+  Tracks tracks(int32_t pair) const {
+    const int32_t n = check(loam_vo_frames_tracks_copy(h_, pair, nullptr, nullptr, nullptr, nullptr, 0));
+    Tracks t;
+    t.prev_xy.resize(static_cast<size_t>(n) * 2);
+    t.curr_xy.resize(static_cast<size_t>(n) * 2);
+    t.status.resize(static_cast<size_t>(n));
+    t.err.resize(static_cast<size_t>(n));
+    if (n) check(loam_vo_frames_tracks_copy(h_, pair, t.prev_xy.data(), t.curr_xy.data(), t.status.data(),
+                                            t.err.data(), n));
+    return t;
   }
   loam_vo_frames* handle() const { return h_; }
 

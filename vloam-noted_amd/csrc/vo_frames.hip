@@ -21,6 +21,9 @@
 //                  stable compaction: the record order is the solve's summation order.  Writes the
 //                  pair's record range for the solve.
 //   k_vo_solve     (vo.hip) one workgroup per pair on those records.
+// A pair given its two images instead (loam_vo_frames_input_images) first runs lk.hip's pyramid and
+// tracking kernels on the same stream; they leave kp0 / kp1 / status as loam_vo_frames_input_tracks
+// would have, and the kernels here see a tracks pair.
 // No workgroup waits on another: the merge is a launch of its own.
 //
 // Records: the right-hand sides are formed in float as the reference does, the 3 x 3 solve with
@@ -34,6 +37,7 @@
 
 #include "depth_dev.h"
 #include "device_res.h"
+#include "lk_dev.h"
 #include "vo_dev.h"
 
 namespace loam {
@@ -45,7 +49,10 @@ constexpr int VM_MAX_SLICES = 16;
 constexpr int VA_THREADS = 1024;  // k_vo_merge / k_vo_assemble: one workgroup per pair
 constexpr int VF_MAX_KEYPOINTS = 1 << 16;
 
-enum { VF_NONE = 0, VF_DESC = 1, VF_TRACKS = 2 };
+// VF_IMAGES is the host's: the kernels are handed such a pair as VF_TRACKS
+enum { VF_NONE = 0, VF_DESC = 1, VF_TRACKS = 2, VF_IMAGES = 3 };
+constexpr size_t VF_MAX_PYRAMID_BYTES = (size_t)2 << 30;
+constexpr int VF_MAX_IMAGE_PAIRS = 32767;  // grid.z of the pyramid kernel = 2 * pairs
 
 struct VfPair {
   int mode;    // VF_*: what the pair's pending input is
@@ -307,6 +314,17 @@ struct loam_vo_frames {
   double* d_x = nullptr;                            // [P][6]
   loam_lm_stats* d_lm = nullptr;
   VfCount* d_cnt = nullptr;
+  // images mode (loam_vo_frames_enable_images)
+  bool lk_on = false;
+  LkPlan lk{};
+  std::vector<VfPair> up;        // pairs as the kernels see them
+  std::vector<LkPair> lk_in;     // the pending images inputs
+  std::vector<LkPair> lk_done;   // the images of the pair's last solve (active = 0: none, or replaced)
+  std::vector<int> tracks_n;     // points of the pair's last tracks / images solve; -1: none, or replaced
+  std::vector<int> tracks_mode;  // VF_TRACKS or VF_IMAGES
+  uint8_t* d_pyr = nullptr;      // [P][2][lk.image_bytes]
+  LkPair* d_lk = nullptr;        // [P]
+  float* d_err = nullptr;        // [P][K]
   DevEvent ev[2];
   float ms = 0.f;
   ~loam_vo_frames() { (void)hipStreamSynchronize(st); }
@@ -364,6 +382,13 @@ int32_t vf_check_input(loam_vo_frames* h, int32_t pair, int32_t n0, int32_t n1, 
     return LOAM_ERR_CAPACITY;
   }
   return LOAM_OK;
+}
+
+// a new input: what the copies read of the pair's last solve is about to be overwritten
+void vf_replace(loam_vo_frames* h, int32_t pair) {
+  h->tracks_n[pair] = -1;
+  h->lk_done[pair].active = 0;
+  h->lk_in[pair].active = 0;
 }
 
 }  // namespace
@@ -434,6 +459,11 @@ int32_t loam_vo_frames_create(const loam_vo_frames_params* p, loam_depth* depth,
   h->x.assign(P * 6, 0.0);
   h->lm.assign(P, loam_lm_stats{});
   h->cnt.assign(P, VfCount{});
+  h->up.assign(P, VfPair{});
+  h->lk_in.assign(P, LkPair{});
+  h->lk_done.assign(P, LkPair{});
+  h->tracks_n.assign(P, -1);
+  h->tracks_mode.assign(P, VF_NONE);
   LOAM_HIP(hipStreamSynchronize(h->st));
   *out = h.release();
   return LOAM_OK;
@@ -467,6 +497,7 @@ int32_t loam_vo_frames_input_descriptors(loam_vo_frames* h, int32_t pair, const 
     LOAM_HIP(hipMemcpyAsync(h->d_kp1 + o, kp1_xy, sizeof(float2) * n1, hipMemcpyHostToDevice, h->st));
   }
   LOAM_HIP(hipStreamSynchronize(h->st));  // the caller's buffers are free after return
+  vf_replace(h, pair);
   h->pairs[pair] = VfPair{VF_DESC, n0, n1, depth_stream_prev};
   return LOAM_OK;
 }
@@ -487,7 +518,75 @@ int32_t loam_vo_frames_input_tracks(loam_vo_frames* h, int32_t pair, const float
     LOAM_HIP(hipMemcpyAsync(h->d_status + o, status, (size_t)n, hipMemcpyHostToDevice, h->st));
   }
   LOAM_HIP(hipStreamSynchronize(h->st));
+  vf_replace(h, pair);
   h->pairs[pair] = VfPair{VF_TRACKS, n, n, depth_stream_prev};
+  return LOAM_OK;
+}
+
+void loam_lk_params_default(loam_lk_params* p) {
+  if (!p) return;
+  *p = loam_lk_params{};
+  p->win = 15;
+  p->max_level = 2;
+  p->max_count = 10;
+  p->epsilon = 0.03;
+  p->min_eig_threshold = 1e-4;
+}
+
+int32_t loam_vo_frames_enable_images(loam_vo_frames* h, const loam_lk_params* p) {
+  if (!h || !p) {
+    set_error("loam_vo_frames_enable_images: null handle or parameters");
+    return LOAM_ERR_ARG;
+  }
+  LkPlan plan;
+  TRY(lk_plan(p, &plan));
+  if (h->lk_on) {
+    set_error("loam_vo_frames_enable_images: the handle already has its pyramids");
+    return LOAM_ERR_STATE;
+  }
+  if (h->P > VF_MAX_IMAGE_PAIRS || plan.image_bytes > VF_MAX_PYRAMID_BYTES / 2 / (size_t)h->P) {
+    set_error("loam_vo_frames_enable_images: more than 2 GiB of pyramids or more than 32767 pairs");
+    return LOAM_ERR_CAPACITY;
+  }
+  LOAM_HIP(hipSetDevice(h->dev));
+  TRY(h->pool.alloc(&h->d_pyr, (size_t)h->P * 2 * plan.image_bytes, h->st));
+  TRY(h->pool.alloc(&h->d_lk, (size_t)h->P, h->st));
+  TRY(h->pool.alloc(&h->d_err, (size_t)h->P * h->K, h->st));
+  LOAM_HIP(hipStreamSynchronize(h->st));
+  h->lk = plan;
+  h->lk_on = true;
+  return LOAM_OK;
+}
+
+int32_t loam_vo_frames_input_images(loam_vo_frames* h, int32_t pair, const uint8_t* img_prev,
+                                    const uint8_t* img_curr, int32_t width, int32_t height, int32_t row_stride,
+                                    const float* pts_xy, int32_t n, int32_t depth_stream_prev) {
+  const char* who = "loam_vo_frames_input_images";
+  TRY(vf_check(h, pair, who));
+  if (!h->lk_on) {
+    set_error(std::string(who) + ": call loam_vo_frames_enable_images first");
+    return LOAM_ERR_STATE;
+  }
+  TRY(vf_check_input(h, pair, n, n, depth_stream_prev, who));
+  if (!img_prev || !img_curr || width <= 0 || height <= 0 || row_stride < width || (n > 0 && !pts_xy)) {
+    set_error(std::string(who) + ": null input or bad image size");
+    return LOAM_ERR_ARG;
+  }
+  if (width > h->lk.max_w || height > h->lk.max_h) {
+    set_error(std::string(who) + ": the image is larger than max_width x max_height");
+    return LOAM_ERR_CAPACITY;
+  }
+  LOAM_HIP(hipSetDevice(h->dev));
+  uint8_t* lvl0 = h->d_pyr + (size_t)pair * 2 * h->lk.image_bytes;  // level 0: dense rows
+  LOAM_HIP(hipMemcpy2DAsync(lvl0, width, img_prev, row_stride, width, height, hipMemcpyHostToDevice, h->st));
+  LOAM_HIP(hipMemcpy2DAsync(lvl0 + h->lk.image_bytes, width, img_curr, row_stride, width, height,
+                            hipMemcpyHostToDevice, h->st));
+  if (n)
+    LOAM_HIP(hipMemcpyAsync(h->d_kp0 + (size_t)pair * h->K, pts_xy, sizeof(float2) * n, hipMemcpyHostToDevice, h->st));
+  LOAM_HIP(hipStreamSynchronize(h->st));
+  vf_replace(h, pair);
+  h->pairs[pair] = VfPair{VF_IMAGES, n, n, depth_stream_prev};
+  h->lk_in[pair] = LkPair{1, width, height, lk_levels(width, height, h->lk.win, h->lk.max_level), n};
   return LOAM_OK;
 }
 
@@ -500,7 +599,7 @@ int32_t loam_vo_frames_set_initial(loam_vo_frames* h, int32_t pair, const double
 int32_t loam_vo_frames_solve(loam_vo_frames* h) {
   if (!h) return LOAM_ERR_ARG;
   int active = 0, max_n0 = 0, max_n1 = 0;
-  bool match = false;
+  bool match = false, images = false;
   for (const VfPair& p : h->pairs) {
     if (p.mode == VF_NONE) continue;
     ++active;
@@ -508,6 +607,7 @@ int32_t loam_vo_frames_solve(loam_vo_frames* h) {
       set_error("loam_vo_frames_solve: depth stream " + std::to_string(p.stream) + " was never processed");
       return LOAM_ERR_STATE;
     }
+    images |= p.mode == VF_IMAGES;
     if (p.mode == VF_DESC && p.n0 > 0 && p.n1 >= 2) {
       match = true;
       max_n0 = std::max(max_n0, p.n0);
@@ -528,9 +628,15 @@ int32_t loam_vo_frames_solve(loam_vo_frames* h) {
   const int qb = (max_n0 + VM_THREADS - 1) / VM_THREADS, tiles = (max_n1 + VM_TILE - 1) / VM_TILE;
   int S = 1;
   if (match) S = std::max(1, std::min({h->S_cap, tiles, (512 + qb * active - 1) / (qb * active)}));
-  LOAM_HIP(hipMemcpyAsync(h->d_pairs, h->pairs.data(), sizeof(VfPair) * P, hipMemcpyHostToDevice, st));
+  h->up = h->pairs;
+  for (VfPair& p : h->up)
+    if (p.mode == VF_IMAGES) p.mode = VF_TRACKS;  // what the pair is once its points are tracked
+  LOAM_HIP(hipMemcpyAsync(h->d_pairs, h->up.data(), sizeof(VfPair) * P, hipMemcpyHostToDevice, st));
   LOAM_HIP(hipMemcpyAsync(h->d_x, h->x0.data(), sizeof(double) * 6 * P, hipMemcpyHostToDevice, st));
+  if (images) LOAM_HIP(hipMemcpyAsync(h->d_lk, h->lk_in.data(), sizeof(LkPair) * P, hipMemcpyHostToDevice, st));
   LOAM_HIP(hipEventRecord(h->ev[0], st));
+  if (images)
+    TRY(lk_launch(h->lk, h->d_lk, h->lk_in.data(), P, h->d_pyr, h->d_kp0, h->d_kp1, h->d_status, h->d_err, K, st));
   if (match) {
     const dim3 grid(qb, S, P);
     if (h->WP == 8)
@@ -560,6 +666,13 @@ int32_t loam_vo_frames_solve(loam_vo_frames* h) {
     h->lm[p] = lm[p];
     h->cnt[p] = cnt[p];
     h->solved[p] = 1;
+    const int mode = h->pairs[p].mode;
+    h->tracks_n[p] = mode == VF_DESC ? -1 : h->pairs[p].n0;
+    h->tracks_mode[p] = mode;
+    if (mode == VF_IMAGES) {
+      h->lk_done[p] = h->lk_in[p];
+      h->lk_in[p].active = 0;
+    }
     h->pairs[p].mode = VF_NONE;
   }
   return LOAM_OK;
@@ -613,6 +726,59 @@ int32_t loam_vo_frames_records_copy(loam_vo_frames* h, int32_t pair, double* rec
   const size_t o = (size_t)pair * h->K;
   if (records) LOAM_HIP(hipMemcpy(records, h->d_records + o * 10, sizeof(double) * 10 * n, hipMemcpyDeviceToHost));
   if (depth0) LOAM_HIP(hipMemcpy(depth0, h->d_depth0 + o, sizeof(float) * n, hipMemcpyDeviceToHost));
+  return n;
+}
+
+int32_t loam_vo_frames_tracks_copy(loam_vo_frames* h, int32_t pair, float* prev_xy, float* curr_xy,
+                                   uint8_t* status, float* err, int32_t cap) {
+  TRY(vf_check(h, pair, "loam_vo_frames_tracks_copy"));
+  if (!h->solved[pair] || h->tracks_n[pair] < 0) {
+    set_error("loam_vo_frames_tracks_copy: the pair has no solved tracks (never solved, solved from descriptors, "
+              "or replaced by a later input)");
+    return LOAM_ERR_STATE;
+  }
+  const int n = h->tracks_n[pair];
+  if (n > cap || n == 0) return n;  // the count only
+  LOAM_HIP(hipSetDevice(h->dev));
+  const size_t o = (size_t)pair * h->K;
+  if (prev_xy) LOAM_HIP(hipMemcpy(prev_xy, h->d_kp0 + o, sizeof(float2) * n, hipMemcpyDeviceToHost));
+  if (curr_xy) LOAM_HIP(hipMemcpy(curr_xy, h->d_kp1 + o, sizeof(float2) * n, hipMemcpyDeviceToHost));
+  if (status) LOAM_HIP(hipMemcpy(status, h->d_status + o, (size_t)n, hipMemcpyDeviceToHost));
+  if (err) {
+    if (h->tracks_mode[pair] == VF_IMAGES)
+      LOAM_HIP(hipMemcpy(err, h->d_err + o, sizeof(float) * n, hipMemcpyDeviceToHost));
+    else
+      std::fill(err, err + n, 0.f);
+  }
+  return n;
+}
+
+int32_t loam_vo_frames_pyramid_copy(loam_vo_frames* h, int32_t pair, int32_t image, int32_t level, uint8_t* out,
+                                    int32_t cap, int32_t* wh) {
+  TRY(vf_check(h, pair, "loam_vo_frames_pyramid_copy"));
+  if (!h->lk_on || !h->lk_done[pair].active) {
+    set_error("loam_vo_frames_pyramid_copy: the pair has no solved images (or a later input replaced them)");
+    return LOAM_ERR_STATE;
+  }
+  const LkPair& L = h->lk_done[pair];
+  if (image < 0 || image > 1 || level < 0 || level >= L.levels) {
+    set_error("loam_vo_frames_pyramid_copy: image is 0 or 1, level below the pair's level count");
+    return LOAM_ERR_ARG;
+  }
+  int w = L.w, ht = L.h;
+  for (int l = 0; l < level; ++l) {
+    w = (w + 1) / 2;
+    ht = (ht + 1) / 2;
+  }
+  if (wh) {
+    wh[0] = w;
+    wh[1] = ht;
+  }
+  const int n = w * ht;
+  if (n > cap || !out) return n;  // the size only
+  LOAM_HIP(hipSetDevice(h->dev));
+  LOAM_HIP(hipMemcpy(out, h->d_pyr + ((size_t)pair * 2 + image) * h->lk.image_bytes + h->lk.lvl_off[level], (size_t)n,
+                     hipMemcpyDeviceToHost));
   return n;
 }
 

@@ -65,6 +65,11 @@ class VOFramesParams(ctypes.Structure):
                 ("max_keypoints", c_i32)]
 
 
+class LKParams(ctypes.Structure):
+    _fields_ = [("max_width", c_i32), ("max_height", c_i32), ("win", c_i32), ("max_level", c_i32),
+                ("max_count", c_i32), ("epsilon", c_d), ("min_eig_threshold", c_d)]
+
+
 class VOFrameStats(ctypes.Structure):
     _fields_ = [("n_knn", c_i32), ("n_matches", c_i32), ("n_gated", c_i32), ("counter32", c_i32),
                 ("counter22", c_i32), ("ms", c_d)]
@@ -175,6 +180,11 @@ SIGNATURES = {
     "loam_vo_frames_result": (c_i32, [vp, c_i32, vp, ctypes.POINTER(LMStats), ctypes.POINTER(VOFrameStats)]),
     "loam_vo_frames_matches_copy": (c_i32, [vp, c_i32, vp, c_i32]),
     "loam_vo_frames_records_copy": (c_i32, [vp, c_i32, vp, vp, c_i32]),
+    "loam_lk_params_default": (None, [ctypes.POINTER(LKParams)]),
+    "loam_vo_frames_enable_images": (c_i32, [vp, ctypes.POINTER(LKParams)]),
+    "loam_vo_frames_input_images": (c_i32, [vp, c_i32, vp, vp, c_i32, c_i32, c_i32, vp, c_i32, c_i32]),
+    "loam_vo_frames_tracks_copy": (c_i32, [vp, c_i32, vp, vp, vp, vp, c_i32]),
+    "loam_vo_frames_pyramid_copy": (c_i32, [vp, c_i32, c_i32, c_i32, vp, c_i32, vp]),
     "loam_lm_solve": (c_i32, [c_i32, vp, c_i32, vp, c_i32, ctypes.POINTER(LMStats)]),
     "loam_lm_normal_equations": (c_i32, [c_i32, vp, c_i32, vp, vp, vp, vp]),
     "loam_voxel_grid": (c_i32, [c_i32, vp, c_i32, c_f, vp, ctypes.POINTER(c_i32)]),

@@ -8,8 +8,9 @@ CostFunctor22 (epipolar).  ``solve`` runs any number of such problems on the dev
 workgroup per problem, every Ceres iteration on the GPU): HuberLoss(0.1), TR-LM, DENSE_QR,
 max_num_iterations = 100 (:70-74).
 
-``VOFrames`` is the whole frame on the device: descriptors (or LK tracks) in, pose out, with the
-matcher, the gate, the depth lookup and the records between them (``vo_factors`` stays the host
+``VOFrames`` is the whole frame on the device: descriptors, LK tracks, or the two images and the
+points to track (pyramidal Lucas-Kanade on the device) in, pose out, with the matcher, the gate,
+the depth lookup and the records between them (``vo_factors`` stays the host
 definition the device records are checked against).  ``vo_to_velo_prior`` turns its solution into
 the prior of the coupled LiDAR odometry.
 """
@@ -84,6 +85,17 @@ def vo_frames_params(P_rect0=None, **kw):
     return p
 
 
+def lk_params(max_width, max_height, **kw):
+    """loam_lk_params: the reference's cv::calcOpticalFlowPyrLK call (window 15, maxLevel 2,
+    COUNT + EPS (10, 0.03), minEigThreshold 1e-4) for images up to max_width x max_height"""
+    p = _core.LKParams()
+    lib().loam_lk_params_default(ctypes.byref(p))
+    p.max_width, p.max_height = int(max_width), int(max_height)
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
 class VOFrames:
     """The VO frame on the device (loam_vo_frames_*): ``n_pairs`` independent frame pairs, each
     from its descriptors (or LK tracks) to angles_0to1 / t_0to1 in one launch sequence per
@@ -132,6 +144,25 @@ class VOFrames:
             raise ValueError("prev_xy, curr_xy and status must have one row per track")
         check(lib().loam_vo_frames_input_tracks(self.h, pair, ptr(a), ptr(b), ptr(s), len(s), depth_stream_prev))
 
+    def enable_images(self, max_width, max_height, **kw):
+        """allocate the image pyramids of every pair (once); kw: loam_lk_params fields"""
+        self.lk = lk_params(max_width, max_height, **kw)
+        check(lib().loam_vo_frames_enable_images(self.h, ctypes.byref(self.lk)))
+
+    def input_images(self, pair, img_prev, img_curr, pts_xy, depth_stream_prev=0):
+        """optical_flow_match from the images: two (height, width) uint8 images of one size (rows
+        may be strided views) and the (n, 2) points of the previous image to track"""
+        a, b = np.asarray(img_prev), np.asarray(img_curr)
+        if a.dtype != np.uint8 or b.dtype != np.uint8 or a.ndim != 2 or a.shape != b.shape:
+            raise ValueError("two 8-bit single-channel images of one size")
+        if a.size and (a.strides[1] != 1 or b.strides != a.strides):
+            a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+        pts = np.ascontiguousarray(pts_xy, dtype=np.float32).reshape(-1, 2)
+        h, w = a.shape
+        check(lib().loam_vo_frames_input_images(self.h, pair, a.ctypes.data, b.ctypes.data, w, h,
+                                                a.strides[0] if a.size else w, ptr(pts), len(pts),
+                                                depth_stream_prev))
+
     def set_initial(self, pair, x6=None):
         x = None if x6 is None else np.ascontiguousarray(x6, dtype=np.float64).reshape(6)
         check(lib().loam_vo_frames_set_initial(self.h, pair, None if x is None else x.ctypes.data))
@@ -161,6 +192,31 @@ class VOFrames:
         if n:
             check(lib().loam_vo_frames_records_copy(self.h, pair, ptr(rec), ptr(d0), n))
         return rec, d0
+
+
+    def tracks(self, pair=0):
+        """(prev_xy (n, 2), curr_xy (n, 2), status (n,) uint8, err (n,)) of the pair's last tracks
+        or images solve; err is LK's (0 for a tracks pair)"""
+        n = check(lib().loam_vo_frames_tracks_copy(self.h, pair, None, None, None, None, 0))
+        prev, curr = np.empty((n, 2), np.float32), np.empty((n, 2), np.float32)
+        status, err = np.empty(n, np.uint8), np.empty(n, np.float32)
+        if n:
+            check(lib().loam_vo_frames_tracks_copy(self.h, pair, ptr(prev), ptr(curr), ptr(status), ptr(err), n))
+        return prev, curr, status, err
+
+    def pyramid(self, pair=0, image=0):
+        """the pyramid levels (list of (h, w) uint8) of the pair's last images solve; image 0 is
+        the previous, 1 the current"""
+        out = []
+        wh = np.zeros(2, np.int32)
+        while True:
+            n = lib().loam_vo_frames_pyramid_copy(self.h, pair, image, len(out), None, 0, ptr(wh))
+            if n == -1 and out:
+                return out  # LOAM_ERR_ARG: past the last level
+            check(n)
+            lvl = np.empty((int(wh[1]), int(wh[0])), np.uint8)
+            check(lib().loam_vo_frames_pyramid_copy(self.h, pair, image, len(out), ptr(lvl), n, None))
+            out.append(lvl)
 
 
 def vo_to_velo_prior(x6, velo_T_cam0):
