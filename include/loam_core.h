@@ -210,6 +210,20 @@ int32_t loam_odometry_output(loam_odometry* h, int32_t stream, double* q_w, doub
 int32_t loam_odometry_last_cloud(loam_odometry* h, int32_t stream, int32_t which, const float** d_ptr);
 int32_t loam_odometry_copy_last(loam_odometry* h, int32_t stream, int32_t which, float* out, int32_t cap);
 int32_t loam_odometry_stats(loam_odometry* h, int32_t stream, loam_odom_stats* st);
+/* for parity tests of the correspondence kernel: what the second outer round of the stream's newest
+ * optimised solve (laser_odometry.cpp:282-485) left on the device for every query, cornerPointsSharp
+ * first, then surfPointsFlat (round 0's records are overwritten).  type: the record type (0 none,
+ * 1 edge, 2 plane); records: 10 doubles per query (type, curr_point[3], a[3], b[3]; edge: a =
+ * last_point_a, b = the unit vector of last_point_a - last_point_b; plane: a = last_point_a, b = the
+ * normalised (a - b) x (a - c), 0 where that product is 0; type 0: a = b = 0); idx: 3 int32 per query,
+ * closestPointInd, minPointInd2, minPointInd3 into laserCloudCornerLast / SurfLast as they were
+ * during that solve, -1 where there is none (the third of a corner query always; all three when the
+ * 1-NN is not within DISTANCE_SQ_THRESHOLD, :299/:397); x0 (may be NULL): the 7 pose values (q xyzw,
+ * t) that round's TransformToStart used.  Copies when cap >= the count; returns the count.
+ * LOAM_ERR_STATE: the stream has not had an optimised solve (the first frame is not optimised).
+ * Valid until the stream's next solve or the handle's reset. */
+int32_t loam_odometry_corr_copy(loam_odometry* h, int32_t stream, double* x0, int32_t* type, double* records,
+                                int32_t* idx, int32_t cap);
 
 /* --------------------------------------------------------------------------------------
  * LaserMapping (laser_mapping.h:85-100) — a handle holds n_streams independent mappers

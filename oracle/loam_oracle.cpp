@@ -1086,6 +1086,12 @@ struct LaserOdometry {
   int corr[4] = {0, 0, 0, 0};
   oracle_lm_stats lm[2] = {};
   double ms = 0;
+  // per outer round of the last optimised solve, for the parity tests: the factors, one
+  // (closestPointInd, minPointInd2, minPointInd3) triple per query (sharp first, then flat; -1:
+  // none) and the pose TransformToStart used
+  std::vector<Factor> factors[2];
+  std::vector<int32_t> corrIdx[2];
+  double roundPose[2][7] = {};
 
   void solve() {
     double t0 = now_ms();
@@ -1097,7 +1103,12 @@ struct LaserOdometry {
           for (int i = 0; i < 4; ++i) para_q[i] = prior_q[i];
           for (int i = 0; i < 3; ++i) para_t[i] = prior_t[i];
         }
-        std::vector<Factor> fs;
+        std::vector<Factor>& fs = factors[opti];
+        std::vector<int32_t>& ci = corrIdx[opti];
+        fs.clear();
+        ci.clear();
+        for (int i = 0; i < 4; ++i) roundPose[opti][i] = para_q[i];
+        for (int i = 0; i < 3; ++i) roundPose[opti][4 + i] = para_t[i];
         int corner_c = 0, plane_c = 0;
         Quat q{para_q[0], para_q[1], para_q[2], para_q[3]};
         V3 t{para_t[0], para_t[1], para_t[2]};
@@ -1140,6 +1151,7 @@ struct LaserOdometry {
             fs.push_back(F);
             corner_c++;
           }
+          ci.insert(ci.end(), {closest, ind2, -1});
         }
         for (const Pt& fp : flat) {
           Pt sel = toStart(fp);
@@ -1177,6 +1189,7 @@ struct LaserOdometry {
               plane_c++;
             }
           }
+          ci.insert(ci.end(), {closest, ind2, ind3});
         }
         corr[opti * 2] = corner_c;
         corr[opti * 2 + 1] = plane_c;
@@ -1626,6 +1639,32 @@ int32_t oracle_odom_stats(oracle_odom* h, int32_t* corr, oracle_lm_stats* lm) {
   return 0;
 }
 double oracle_odom_ms(oracle_odom* h) { return h->o.ms; }
+int32_t oracle_odom_factor_count(oracle_odom* h, int32_t round) {
+  return static_cast<int32_t>(h->o.factors[round & 1].size());
+}
+int32_t oracle_odom_factors(oracle_odom* h, int32_t round, double* out) {
+  const auto& fs = h->o.factors[round & 1];
+  for (size_t i = 0; i < fs.size(); ++i) {
+    double* r = out + i * 10;
+    r[0] = fs[i].type;
+    for (int k = 0; k < 3; ++k) {
+      r[1 + k] = fs[i].p[k];
+      r[4 + k] = fs[i].a[k];
+      r[7 + k] = fs[i].b[k];
+    }
+  }
+  return static_cast<int32_t>(fs.size());
+}
+// 3 int32 per query of that round; returns the number of queries
+int32_t oracle_odom_corr_idx(oracle_odom* h, int32_t round, int32_t* out) {
+  const auto& ci = h->o.corrIdx[round & 1];
+  if (out) std::copy(ci.begin(), ci.end(), out);
+  return static_cast<int32_t>(ci.size() / 3);
+}
+int32_t oracle_odom_round_pose(oracle_odom* h, int32_t round, double* x7) {
+  for (int i = 0; i < 7; ++i) x7[i] = h->o.roundPose[round & 1][i];
+  return 0;
+}
 
 // ---- mapping
 struct oracle_map {

@@ -99,6 +99,14 @@ int32_t oracle_odom_copy(oracle_odom* h, int32_t which, float* out);
 /* per-round stats: corner/plane correspondences + LM stats of the last solve (2 rounds) */
 int32_t oracle_odom_stats(oracle_odom* h, int32_t* corr /*[4]*/, oracle_lm_stats* lm /*[2]*/);
 double oracle_odom_ms(oracle_odom* h);
+/* of round r (0/1) of the last optimised solve: the factor list (10 doubles per factor: type 1 edge
+ * p, a, b = the two last-cloud points; type 2 plane p, a = j, b = unit normal), one (closestPointInd,
+ * minPointInd2, minPointInd3) triple per query (sharp first, then flat; -1: none; out may be NULL;
+ * returns the number of queries), and the pose TransformToStart used */
+int32_t oracle_odom_factor_count(oracle_odom* h, int32_t round);
+int32_t oracle_odom_factors(oracle_odom* h, int32_t round, double* out);
+int32_t oracle_odom_corr_idx(oracle_odom* h, int32_t round, int32_t* out);
+int32_t oracle_odom_round_pose(oracle_odom* h, int32_t round, double* x7);
 
 /* ---- LaserMapping (laser_mapping.cpp:147-814) ---- */
 typedef struct oracle_map oracle_map;

@@ -62,6 +62,10 @@ def lib():
             "oracle_odom_copy": (c_i32, [vp, c_i32, vp]),
             "oracle_odom_stats": (c_i32, [vp, vp, ctypes.POINTER(LMStats)]),
             "oracle_odom_ms": (c_d, [vp]),
+            "oracle_odom_factor_count": (c_i32, [vp, c_i32]),
+            "oracle_odom_factors": (c_i32, [vp, c_i32, vp]),
+            "oracle_odom_corr_idx": (c_i32, [vp, c_i32, vp]),
+            "oracle_odom_round_pose": (c_i32, [vp, c_i32, vp]),
             "oracle_map_create": (vp, [c_f, c_f]),
             "oracle_map_destroy": (None, [vp]),
             "oracle_map_input": (c_i32, [vp, vp, c_i32, vp, c_i32, vp, c_i32, vp, vp, c_i32]),
@@ -287,6 +291,27 @@ class LaserOdometry:
         lm = (LMStats * 2)()
         lib().oracle_odom_stats(self.h, _ptr(corr), lm)
         return corr, [lm[0], lm[1]]
+
+    def factors(self, rnd):
+        """(n, 10) factor list of round rnd of the last optimised solve (edge: a, b the two points)"""
+        n = lib().oracle_odom_factor_count(self.h, rnd)
+        out = np.empty((n, 10))
+        if n:
+            lib().oracle_odom_factors(self.h, rnd, _ptr(out))
+        return out
+
+    def corr_idx(self, rnd):
+        """(nq, 3) int32 closestPointInd, minPointInd2, minPointInd3 per query of that round (-1: none)"""
+        n = lib().oracle_odom_corr_idx(self.h, rnd, None)
+        out = np.empty((n, 3), dtype=np.int32)
+        if n:
+            lib().oracle_odom_corr_idx(self.h, rnd, _ptr(out))
+        return out
+
+    def round_pose(self, rnd):
+        x = np.empty(7)
+        lib().oracle_odom_round_pose(self.h, rnd, _ptr(x))
+        return x
 
     @property
     def ms(self):

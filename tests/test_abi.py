@@ -23,7 +23,7 @@ def test_header_declares_the_api():
     names = declared()
     for must in ("loam_scanreg_create", "loam_scanreg_input", "loam_mapper_create", "loam_mapper_input",
                  "loam_mapper_solve", "loam_mapper_pose", "loam_lm_solve", "loam_voxel_grid",
-                 "loam_mapper_corr_copy", "loam_corr_geometry"):
+                 "loam_mapper_corr_copy", "loam_corr_geometry", "loam_odometry_corr_copy"):
         assert must in names
 
 
@@ -146,3 +146,4 @@ def test_new_entry_points_validate_arguments():
     assert L.loam_corr_geometry(0, None, 1, 0, None, None, None) == -1  # neighbour sets missing
     assert L.loam_corr_geometry(0, None, 0, 2, None, None, None) == -1  # which: 0 line, 1 plane
     assert L.loam_mapper_corr_copy(None, 0, None, None, None, None, 0) == -1
+    assert L.loam_odometry_corr_copy(None, 0, None, None, None, None, 0) == -1

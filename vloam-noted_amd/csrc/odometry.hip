@@ -63,6 +63,7 @@ struct OdomFrame {
   int err;
   int has_prior;   // !detach_VO_LO: every outer round starts from `prior` (laser_odometry.cpp:237-250)
   double prior[7];
+  double x0[2][7];  // the pose each round's k_od_corr transformed its queries with (loam_odometry_corr_copy)
   LmState lm[2];
 };
 
@@ -77,6 +78,7 @@ struct OdomDev {
   uint4* ltab[2];      // [B][OD_TAB] {key, start, count, -}
   uint32_t* scratch;   // [B][2][cap] slot << 16 | rank (build)
   int* r_type;         // records [B][OD_MAXQ]
+  int3* r_idx;         // [B][OD_MAXQ] closest, minPointInd2, minPointInd3 (-1: none; loam_odometry_corr_copy)
   float *r_px, *r_py, *r_pz;
   double* r_a[3];
   double* r_b[3];
@@ -109,11 +111,12 @@ __device__ inline uint4 od_find(const uint4* tab, uint32_t key) {
   }
   return make_uint4(OD_EMPTY, 0, 0, 0);
 }
-// squared distance from q to cell (x, y, z) (0 inside)
+// squared distance from q to cell (x, y, z) (0 inside).  od_cell clamps, so a border cell also
+// holds every point beyond it: its box has no bound on that side.
 __device__ inline float od_gap2(float qx, float qy, float qz, int x, int y, int z) {
   auto g = [](float q, int c) {
     const float lo = (float)(c - OD_ORIGIN) * OD_CELL, hi = lo + OD_CELL;
-    return q < lo ? lo - q : (q > hi ? q - hi : 0.0f);
+    return (q < lo && c > 0) ? lo - q : ((q > hi && c < 511) ? q - hi : 0.0f);
   };
   const float gx = g(qx, x), gy = g(qy, y), gz = g(qz, z);
   return gx * gx + gy * gy + gz * gz;
@@ -358,7 +361,11 @@ __global__ void __launch_bounds__(OD_QTHREADS) k_od_corr(OdomDev D, int round, i
 #pragma unroll
   for (int i = 0; i < 7; ++i) X[i] = x0[i];
   if (blk == 0 && threadIdx.x < LM_SYNC_WORDS) D.lm_sync[((size_t)s * 2 + round) * LM_SYNC_WORDS + threadIdx.x] = 0;
-  if (blk == 0 && threadIdx.x == 0) lm_init(F.lm[round], X, 4, true);
+  if (blk == 0 && threadIdx.x == 0) {
+    lm_init(F.lm[round], X, 4, true);
+#pragma unroll
+    for (int i = 0; i < 7; ++i) F.x0[round][i] = X[i];
+  }
   const int ns = F.n_in[0], nf = F.n_in[2];
   const size_t rb = (size_t)s * OD_MAXQ;
   const size_t cb = (size_t)s * D.cap;
@@ -373,6 +380,7 @@ __global__ void __launch_bounds__(OD_QTHREADS) k_od_corr(OdomDev D, int round, i
     const int* sidx = D.lsidx[c] + cb;
     const float4* last = D.last[c] + cb;
     int type = 0;
+    int3 ind = make_int3(-1, -1, -1);
     double a[3] = {0, 0, 0}, b[3] = {0, 0, 0};
     // 1-NN (FLANN L2_Simple<float>, ties by index)
     OdNear n1{INFINITY, 0xFFFFFFFFu, -1};
@@ -391,6 +399,7 @@ __global__ void __launch_bounds__(OD_QTHREADS) k_od_corr(OdomDev D, int round, i
       const int nl = F.n_last[c];
       OdNear b2, b3;
       od_ring_scans(last, nl, cl, cid, c, sel, lane, b2, b3);
+      ind = make_int3(cl, b2.j, b3.j);
       const float4 pa = last[cl];
       if (c == 0 && b2.j >= 0) {
         // LidarEdgeFactor(curr, a = last[cl], b = last[ind2]): r = (lp - a) x e, e = (a - b)/|a - b|
@@ -416,6 +425,7 @@ __global__ void __launch_bounds__(OD_QTHREADS) k_od_corr(OdomDev D, int round, i
     }
     if (lane == 0) {
       D.r_type[rb + q] = type;
+      D.r_idx[rb + q] = ind;
       D.r_px[rb + q] = cp.x;
       D.r_py[rb + q] = cp.y;
       D.r_pz[rb + q] = cp.z;
@@ -485,6 +495,7 @@ struct OdomHost {
   int frame_count = 0;
   bool pending = false;
   bool prior_set = false;  // loam_odometry_set_prior for the next solve
+  int corr_n = -1;         // queries of the newest optimised solve (loam_odometry_corr_copy); -1: none yet
   double prior[7] = {0, 0, 0, 1, 0, 0, 0};
   loam_odom_stats st{};
 };
@@ -552,6 +563,7 @@ int32_t loam_odometry_create(const loam_params* p, int32_t device, int32_t n_str
   }
   TRY(alloc(D.scratch, B * 2 * cap));
   TRY(alloc(D.r_type, B * (size_t)OD_MAXQ));
+  TRY(alloc(D.r_idx, B * (size_t)OD_MAXQ));
   TRY(alloc(D.r_px, B * (size_t)OD_MAXQ));
   TRY(alloc(D.r_py, B * (size_t)OD_MAXQ));
   TRY(alloc(D.r_pz, B * (size_t)OD_MAXQ));
@@ -705,6 +717,7 @@ int32_t loam_odometry_solve(loam_odometry* h) {
     err |= F.err;
     loam_odom_stats& S = H.st;
     S = loam_odom_stats{};
+    H.corr_n = F.inited ? F.n_in[0] + F.n_in[2] : -1;
     if (F.inited) {
       // laser_odometry.cpp:524-527: t_w += q_w * t_lc ; q_w = q_w * q_lc
       const dq qw{H.q_w[0], H.q_w[1], H.q_w[2], H.q_w[3]};
@@ -794,6 +807,45 @@ int32_t loam_odometry_copy_last(loam_odometry* h, int32_t s, int32_t which, floa
   if (!out || cap < n) return LOAM_ERR_ARG;
   LOAM_HIP(hipSetDevice(h->dev));
   if (n) LOAM_HIP(hipMemcpy(out, p, sizeof(float4) * n, hipMemcpyDeviceToHost));
+  return n;
+}
+
+int32_t loam_odometry_corr_copy(loam_odometry* h, int32_t s, double* x0, int32_t* type, double* records, int32_t* idx,
+                                int32_t cap) {
+  TRY(od_check(h, s));
+  if (cap < 0 || (cap > 0 && (!type || !records || !idx))) return LOAM_ERR_ARG;
+  const int32_t n = h->hs[s].corr_n;
+  if (n < 0) {
+    set_error("loam_odometry_corr_copy: the stream has not had an optimised solve");
+    return LOAM_ERR_STATE;
+  }
+  if (x0) std::copy(h->hf[s].x0[1], h->hf[s].x0[1] + 7, x0);
+  if (n > cap || n == 0) return n;  // the count only
+  LOAM_HIP(hipSetDevice(h->dev));
+  const OdomDev& D = h->D;
+  const size_t rb = (size_t)s * OD_MAXQ;
+  std::vector<float> p[3];
+  std::vector<double> ab[6];
+  const float* dp[3] = {D.r_px, D.r_py, D.r_pz};
+  LOAM_HIP(hipMemcpy(type, D.r_type + rb, sizeof(int) * n, hipMemcpyDeviceToHost));
+  LOAM_HIP(hipMemcpy(idx, D.r_idx + rb, sizeof(int3) * n, hipMemcpyDeviceToHost));
+  for (int k = 0; k < 3; ++k) {
+    p[k].resize(n);
+    ab[k].resize(n);
+    ab[3 + k].resize(n);
+    LOAM_HIP(hipMemcpy(p[k].data(), dp[k] + rb, sizeof(float) * n, hipMemcpyDeviceToHost));
+    LOAM_HIP(hipMemcpy(ab[k].data(), D.r_a[k] + rb, sizeof(double) * n, hipMemcpyDeviceToHost));
+    LOAM_HIP(hipMemcpy(ab[3 + k].data(), D.r_b[k] + rb, sizeof(double) * n, hipMemcpyDeviceToHost));
+  }
+  for (int32_t i = 0; i < n; ++i) {
+    double* r = records + (size_t)i * 10;
+    r[0] = type[i];
+    for (int k = 0; k < 3; ++k) {
+      r[1 + k] = p[k][i];
+      r[4 + k] = ab[k][i];
+      r[7 + k] = ab[3 + k][i];
+    }
+  }
   return n;
 }
 

@@ -118,6 +118,7 @@ SIGNATURES = {
     "loam_odometry_last_cloud": (c_i32, [vp, c_i32, c_i32, ctypes.POINTER(vp)]),
     "loam_odometry_copy_last": (c_i32, [vp, c_i32, c_i32, vp, c_i32]),
     "loam_odometry_stats": (c_i32, [vp, c_i32, ctypes.POINTER(OdomStats)]),
+    "loam_odometry_corr_copy": (c_i32, [vp, c_i32, vp, vp, vp, vp, c_i32]),
     "loam_mapper_create": (c_i32, [ctypes.POINTER(Params), c_i32, c_i32, ctypes.POINTER(vp)]),
     "loam_mapper_destroy": (c_i32, [vp]),
     "loam_mapper_reset": (c_i32, [vp]),

@@ -85,6 +85,20 @@ class BatchOdometry:
         check(lib().loam_odometry_stats(self.h, stream, ctypes.byref(st)))
         return st
 
+    def corr(self, stream=0):
+        """what the second outer round of the stream's newest optimised solve left for every query,
+        cornerPointsSharp first, then surfPointsFlat (loam_odometry_corr_copy): x0 (7,) the pose
+        TransformToStart used, type (n,) int32, records (n, 10) float64 (type, curr point, a, b),
+        idx (n, 3) int32 closest / minPointInd2 / minPointInd3 (-1: none)"""
+        x0 = np.empty(7)
+        n = check(lib().loam_odometry_corr_copy(self.h, stream, ptr(x0), None, None, None, 0))
+        typ = np.empty(n, dtype=np.int32)
+        rec = np.empty((n, 10))
+        idx = np.empty((n, 3), dtype=np.int32)
+        if n:
+            check(lib().loam_odometry_corr_copy(self.h, stream, ptr(x0), ptr(typ), ptr(rec), ptr(idx), n))
+        return x0, typ, rec, idx
+
 
 class LaserOdometry:
     """Single-stream drop-in with the reference method names."""
