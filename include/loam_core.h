@@ -535,8 +535,10 @@ int32_t loam_vo_solve(int32_t device, int32_t n_problems, const int32_t* offsets
  * previous point (:371), the CostFunctor32 / CostFunctor22 records (:400-474) and the solve, as
  * one launch sequence.  optical_flow_match = true: either the LK tracks, or the two images and
  * the points to track (loam_vo_frames_input_images below: the cv::calcOpticalFlowPyrLK call of
- * ImageUtil::calculateOpticalFlow runs on the device in front of the rest).  Keypoint detection
- * (ORB, or goodFeaturesToTrack for the optical-flow mode) and ORB description stay with OpenCV.
+ * ImageUtil::calculateOpticalFlow runs on the device in front of the rest), or the two images
+ * alone (loam_vo_frames_input_image_pair: the cv::goodFeaturesToTrack call of
+ * ImageUtil::detKeypoints runs on the device in front of the tracker).  ORB detection and
+ * description stay with OpenCV.
  * ------------------------------------------------------------------------------------ */
 typedef struct loam_vo_frames loam_vo_frames;
 typedef struct loam_vo_frames_params {
@@ -627,6 +629,42 @@ int32_t loam_vo_frames_tracks_copy(loam_vo_frames* h, int32_t pair, float* prev_
  * height; return width * height.  LOAM_ERR_ARG: a level the pair does not have */
 int32_t loam_vo_frames_pyramid_copy(loam_vo_frames* h, int32_t pair, int32_t image, int32_t level, uint8_t* out,
                                     int32_t cap, int32_t* wh);
+
+/* optical_flow_match = true from the two images alone: cv::goodFeaturesToTrack (OpenCV 4, 8-bit
+ * single channel, no mask, gradientSize 3, useHarrisDetector false) as ImageUtil::detKeypoints calls
+ * it (image_util.cpp:8-71) runs on the device in front of the tracker.  The three box sums of the
+ * derivative products are exact integers converted to float once (OpenCV adds float products in an
+ * order its SIMD / IPP dispatch decides); everything else follows OpenCV operation by operation,
+ * the order of equal eigenvalues (higher linear index first) included. */
+typedef struct loam_gftt_params {
+  int32_t max_corners;     /* 1024; 1..max_keypoints */
+  double  quality_level;   /* 0.03; > 0 */
+  double  min_distance;    /* 7.5 (block_size * 1.5, image_util.cpp:29); >= 0, finite; < 1: no suppression */
+  int32_t block_size;      /* 5; 2..15 */
+  int32_t max_candidates;  /* 65536 per image; 1..4194304 */
+} loam_gftt_params;
+void    loam_gftt_params_default(loam_gftt_params* p);
+/* allocates the eigenvalue planes, candidate lists and corner grids of every pair (once per
+ * handle, after loam_vo_frames_enable_images, whose max_width x max_height they are sized for).
+ * LOAM_ERR_ARG: a parameter outside its range; LOAM_ERR_STATE: before loam_vo_frames_enable_images,
+ * or already enabled; LOAM_ERR_CAPACITY: more than 2 GiB of them, or an image side over 65535 */
+int32_t loam_vo_frames_enable_detection(loam_vo_frames* h, const loam_gftt_params* p);
+/* previous and current image as for loam_vo_frames_input_images, and no points: the solve detects
+ * them on the previous image (detect_on 0, the textbook order) or on the current one (detect_on 1,
+ * the reference's calculateOpticalFlow(images[1 - i], images[i], keypoints[i])); either way they
+ * are tracked from img_prev to img_curr and the solve goes on as for loam_vo_frames_input_images.
+ * loam_vo_frame_stats.n_knn is the corner count; loam_vo_frames_tracks_copy returns the corners as
+ * prev_xy, in selection order.  An image with more than max_candidates candidates: the pair solves
+ * with no points and its loam_vo_frames_result returns LOAM_ERR_CAPACITY (the text names
+ * max_candidates and the count); other pairs are unaffected.  LOAM_ERR_STATE before
+ * loam_vo_frames_enable_detection */
+int32_t loam_vo_frames_input_image_pair(loam_vo_frames* h, int32_t pair, const uint8_t* img_prev,
+                                        const uint8_t* img_curr, int32_t width, int32_t height,
+                                        int32_t row_stride, int32_t detect_on, int32_t depth_stream_prev);
+/* for parity tests: the minimum-eigenvalue plane (cornerMinEigenVal) of the pair's last detection,
+ * dense rows; wh (may be NULL) gets its width and height; copy when cap >= width * height; return
+ * width * height */
+int32_t loam_vo_frames_eig_copy(loam_vo_frames* h, int32_t pair, float* out, int32_t cap, int32_t* wh);
 
 /* --------------------------------------------------------------------------------------
  * Device LM engine on an explicit factor list (lidarFactor.hpp + Ceres TR-LM).  Factor

@@ -246,6 +246,12 @@ inline loam_lk_params default_lk_params(int32_t max_width, int32_t max_height) {
   return p;
 }
 
+inline loam_gftt_params default_gftt_params() {
+  loam_gftt_params p;
+  loam_gftt_params_default(&p);
+  return p;
+}
+
 inline loam_vo_frames_params default_vo_frames_params() {
   loam_vo_frames_params p;
   loam_vo_frames_params_default(&p);
@@ -294,6 +300,17 @@ class VisualOdometryFrames {
                    int32_t row_stride, const float* pts_xy, int32_t n, int32_t depth_stream_prev) {
     check(loam_vo_frames_input_images(h_, pair, img_prev, img_curr, width, height, row_stride, pts_xy, n,
                                       depth_stream_prev));
+  }
+  // once, after enableImages and before inputImagePair: the detector's buffers of every pair
+  void enableDetection(const loam_gftt_params& p = default_gftt_params()) {
+    check(loam_vo_frames_enable_detection(h_, &p));
+  }
+  // optical_flow_match from the two images alone: ImageUtil::detKeypoints' goodFeaturesToTrack on
+  // img_prev (detect_on 0) or img_curr (detect_on 1, the reference's order), then as inputImages
+  void inputImagePair(int32_t pair, const uint8_t* img_prev, const uint8_t* img_curr, int32_t width, int32_t height,
+                      int32_t row_stride, int32_t detect_on, int32_t depth_stream_prev) {
+    check(loam_vo_frames_input_image_pair(h_, pair, img_prev, img_curr, width, height, row_stride, detect_on,
+                                          depth_stream_prev));
   }
   // angles_0to1 ++ t_0to1 the solves start from; nullptr: zeros (reset_VO_to_identity)
   void setInitial(int32_t pair, const double* x6 = nullptr) { check(loam_vo_frames_set_initial(h_, pair, x6)); }

@@ -23,7 +23,9 @@
 //   k_vo_solve     (vo.hip) one workgroup per pair on those records.
 // A pair given its two images instead (loam_vo_frames_input_images) first runs lk.hip's pyramid and
 // tracking kernels on the same stream; they leave kp0 / kp1 / status as loam_vo_frames_input_tracks
-// would have, and the kernels here see a tracks pair.
+// would have, and the kernels here see a tracks pair.  A pair given the images alone
+// (loam_vo_frames_input_image_pair) runs gftt.hip's corner detection in front of that: it leaves kp0
+// and, on the device, the point count in the pair tables the tracker and the kernels here read.
 // No workgroup waits on another: the merge is a launch of its own.
 //
 // Records: the right-hand sides are formed in float as the reference does, the 3 x 3 solve with
@@ -37,6 +39,7 @@
 
 #include "depth_dev.h"
 #include "device_res.h"
+#include "gftt_dev.h"
 #include "lk_dev.h"
 #include "vo_dev.h"
 
@@ -49,16 +52,9 @@ constexpr int VM_MAX_SLICES = 16;
 constexpr int VA_THREADS = 1024;  // k_vo_merge / k_vo_assemble: one workgroup per pair
 constexpr int VF_MAX_KEYPOINTS = 1 << 16;
 
-// VF_IMAGES is the host's: the kernels are handed such a pair as VF_TRACKS
-enum { VF_NONE = 0, VF_DESC = 1, VF_TRACKS = 2, VF_IMAGES = 3 };
 constexpr size_t VF_MAX_PYRAMID_BYTES = (size_t)2 << 30;
+constexpr size_t VF_MAX_DETECT_BYTES = (size_t)2 << 30;  // eigenvalue planes + candidate keys + cell grids
 constexpr int VF_MAX_IMAGE_PAIRS = 32767;  // grid.z of the pyramid kernel = 2 * pairs
-
-struct VfPair {
-  int mode;    // VF_*: what the pair's pending input is
-  int n0, n1;  // descriptors of image 0 / 1 (tracks: n0 = n1 = n)
-  int stream;  // depth stream of the previous frame
-};
 
 struct VfCount {
   int n_knn, n_matches, n_gated, counter32, counter22;
@@ -325,6 +321,13 @@ struct loam_vo_frames {
   uint8_t* d_pyr = nullptr;      // [P][2][lk.image_bytes]
   LkPair* d_lk = nullptr;        // [P]
   float* d_err = nullptr;        // [P][K]
+  // detect mode (loam_vo_frames_enable_detection)
+  bool gf_on = false;
+  GfPlan gf{};
+  GfBuffers gfb{};
+  std::vector<GfPair> gf_in;     // the pending detect inputs
+  std::vector<GfPair> gf_done;   // the image of the pair's last detect solve (active = 0: none, or replaced)
+  std::vector<GfState> gf_state; // what the pair's last solve left (n_cand = 0 for the other modes)
   DevEvent ev[2];
   float ms = 0.f;
   ~loam_vo_frames() { (void)hipStreamSynchronize(st); }
@@ -389,6 +392,28 @@ void vf_replace(loam_vo_frames* h, int32_t pair) {
   h->tracks_n[pair] = -1;
   h->lk_done[pair].active = 0;
   h->lk_in[pair].active = 0;
+  h->gf_done[pair].active = 0;
+  h->gf_in[pair].active = 0;
+}
+
+// the checks and the copies input_images and input_image_pair share: both images into level 0 of
+// the pair's pyramid slot
+int32_t vf_put_images(loam_vo_frames* h, int32_t pair, const uint8_t* img_prev, const uint8_t* img_curr,
+                      int32_t width, int32_t height, int32_t row_stride, const char* who) {
+  if (!img_prev || !img_curr || width <= 0 || height <= 0 || row_stride < width) {
+    set_error(std::string(who) + ": null input or bad image size");
+    return LOAM_ERR_ARG;
+  }
+  if (width > h->lk.max_w || height > h->lk.max_h) {
+    set_error(std::string(who) + ": the image is larger than max_width x max_height");
+    return LOAM_ERR_CAPACITY;
+  }
+  LOAM_HIP(hipSetDevice(h->dev));
+  uint8_t* lvl0 = h->d_pyr + (size_t)pair * 2 * h->lk.image_bytes;  // level 0: dense rows
+  LOAM_HIP(hipMemcpy2DAsync(lvl0, width, img_prev, row_stride, width, height, hipMemcpyHostToDevice, h->st));
+  LOAM_HIP(hipMemcpy2DAsync(lvl0 + h->lk.image_bytes, width, img_curr, row_stride, width, height,
+                            hipMemcpyHostToDevice, h->st));
+  return LOAM_OK;
 }
 
 }  // namespace
@@ -462,6 +487,9 @@ int32_t loam_vo_frames_create(const loam_vo_frames_params* p, loam_depth* depth,
   h->up.assign(P, VfPair{});
   h->lk_in.assign(P, LkPair{});
   h->lk_done.assign(P, LkPair{});
+  h->gf_in.assign(P, GfPair{});
+  h->gf_done.assign(P, GfPair{});
+  h->gf_state.assign(P, GfState{});
   h->tracks_n.assign(P, -1);
   h->tracks_mode.assign(P, VF_NONE);
   LOAM_HIP(hipStreamSynchronize(h->st));
@@ -568,25 +596,89 @@ int32_t loam_vo_frames_input_images(loam_vo_frames* h, int32_t pair, const uint8
     return LOAM_ERR_STATE;
   }
   TRY(vf_check_input(h, pair, n, n, depth_stream_prev, who));
-  if (!img_prev || !img_curr || width <= 0 || height <= 0 || row_stride < width || (n > 0 && !pts_xy)) {
+  if (n > 0 && !pts_xy) {
     set_error(std::string(who) + ": null input or bad image size");
     return LOAM_ERR_ARG;
   }
-  if (width > h->lk.max_w || height > h->lk.max_h) {
-    set_error(std::string(who) + ": the image is larger than max_width x max_height");
-    return LOAM_ERR_CAPACITY;
-  }
-  LOAM_HIP(hipSetDevice(h->dev));
-  uint8_t* lvl0 = h->d_pyr + (size_t)pair * 2 * h->lk.image_bytes;  // level 0: dense rows
-  LOAM_HIP(hipMemcpy2DAsync(lvl0, width, img_prev, row_stride, width, height, hipMemcpyHostToDevice, h->st));
-  LOAM_HIP(hipMemcpy2DAsync(lvl0 + h->lk.image_bytes, width, img_curr, row_stride, width, height,
-                            hipMemcpyHostToDevice, h->st));
+  TRY(vf_put_images(h, pair, img_prev, img_curr, width, height, row_stride, who));
   if (n)
     LOAM_HIP(hipMemcpyAsync(h->d_kp0 + (size_t)pair * h->K, pts_xy, sizeof(float2) * n, hipMemcpyHostToDevice, h->st));
   LOAM_HIP(hipStreamSynchronize(h->st));
   vf_replace(h, pair);
   h->pairs[pair] = VfPair{VF_IMAGES, n, n, depth_stream_prev};
   h->lk_in[pair] = LkPair{1, width, height, lk_levels(width, height, h->lk.win, h->lk.max_level), n};
+  return LOAM_OK;
+}
+
+void loam_gftt_params_default(loam_gftt_params* p) {
+  if (!p) return;
+  *p = loam_gftt_params{};
+  p->max_corners = 1024;
+  p->quality_level = 0.03;
+  p->min_distance = 7.5;
+  p->block_size = 5;
+  p->max_candidates = 65536;
+}
+
+int32_t loam_vo_frames_enable_detection(loam_vo_frames* h, const loam_gftt_params* p) {
+  const char* who = "loam_vo_frames_enable_detection";
+  if (!h || !p) {
+    set_error(std::string(who) + ": null handle or parameters");
+    return LOAM_ERR_ARG;
+  }
+  if (!h->lk_on) {
+    set_error(std::string(who) + ": call loam_vo_frames_enable_images first");
+    return LOAM_ERR_STATE;
+  }
+  if (h->gf_on) {
+    set_error(std::string(who) + ": the handle already detects");
+    return LOAM_ERR_STATE;
+  }
+  GfPlan plan;
+  TRY(gftt_plan(p, h->K, h->lk.max_w, h->lk.max_h, &plan));
+  const size_t per_image = sizeof(float) * plan.eig_stride + sizeof(uint64_t) * plan.cand_pad +
+                           (sizeof(uint32_t) * plan.cell_cap + sizeof(int)) * plan.cell_stride;
+  if (per_image > VF_MAX_DETECT_BYTES / (size_t)h->P) {
+    set_error(std::string(who) + ": more than 2 GiB of eigenvalue planes, candidate keys and cell grids");
+    return LOAM_ERR_CAPACITY;
+  }
+  LOAM_HIP(hipSetDevice(h->dev));
+  const size_t P = h->P;
+  GfBuffers B{};
+  TRY(h->pool.alloc(&B.gf, P, h->st));
+  TRY(h->pool.alloc(&B.state, P, h->st));
+  TRY(h->pool.alloc(&B.eig, P * plan.eig_stride, h->st));
+  TRY(h->pool.alloc(&B.keys, P * plan.cand_pad, h->st));
+  TRY(h->pool.alloc(&B.cells, P * plan.cell_stride * plan.cell_cap, h->st));
+  TRY(h->pool.alloc(&B.cell_cnt, P * plan.cell_stride, h->st));
+  LOAM_HIP(hipStreamSynchronize(h->st));
+  h->gf = plan;
+  h->gfb = B;
+  h->gf_on = true;
+  return LOAM_OK;
+}
+
+int32_t loam_vo_frames_input_image_pair(loam_vo_frames* h, int32_t pair, const uint8_t* img_prev,
+                                        const uint8_t* img_curr, int32_t width, int32_t height,
+                                        int32_t row_stride, int32_t detect_on, int32_t depth_stream_prev) {
+  const char* who = "loam_vo_frames_input_image_pair";
+  TRY(vf_check(h, pair, who));
+  if (!h->gf_on) {
+    set_error(std::string(who) + ": call loam_vo_frames_enable_detection first");
+    return LOAM_ERR_STATE;
+  }
+  TRY(vf_check_input(h, pair, 0, 0, depth_stream_prev, who));
+  if (detect_on < 0 || detect_on > 1) {
+    set_error(std::string(who) + ": detect_on is 0 (the previous image) or 1 (the current one)");
+    return LOAM_ERR_ARG;
+  }
+  TRY(vf_put_images(h, pair, img_prev, img_curr, width, height, row_stride, who));
+  LOAM_HIP(hipStreamSynchronize(h->st));
+  vf_replace(h, pair);
+  h->pairs[pair] = VfPair{VF_DETECT, 0, 0, depth_stream_prev};  // the count is the device's
+  // n: the width of the tracker's grid; the detection writes the pair's own count over it
+  h->lk_in[pair] = LkPair{1, width, height, lk_levels(width, height, h->lk.win, h->lk.max_level), h->gf.max_corners};
+  h->gf_in[pair] = GfPair{1, width, height, detect_on};
   return LOAM_OK;
 }
 
@@ -599,7 +691,7 @@ int32_t loam_vo_frames_set_initial(loam_vo_frames* h, int32_t pair, const double
 int32_t loam_vo_frames_solve(loam_vo_frames* h) {
   if (!h) return LOAM_ERR_ARG;
   int active = 0, max_n0 = 0, max_n1 = 0;
-  bool match = false, images = false;
+  bool match = false, images = false, detect = false;
   for (const VfPair& p : h->pairs) {
     if (p.mode == VF_NONE) continue;
     ++active;
@@ -607,7 +699,8 @@ int32_t loam_vo_frames_solve(loam_vo_frames* h) {
       set_error("loam_vo_frames_solve: depth stream " + std::to_string(p.stream) + " was never processed");
       return LOAM_ERR_STATE;
     }
-    images |= p.mode == VF_IMAGES;
+    images |= p.mode == VF_IMAGES || p.mode == VF_DETECT;
+    detect |= p.mode == VF_DETECT;
     if (p.mode == VF_DESC && p.n0 > 0 && p.n1 >= 2) {
       match = true;
       max_n0 = std::max(max_n0, p.n0);
@@ -630,11 +723,16 @@ int32_t loam_vo_frames_solve(loam_vo_frames* h) {
   if (match) S = std::max(1, std::min({h->S_cap, tiles, (512 + qb * active - 1) / (qb * active)}));
   h->up = h->pairs;
   for (VfPair& p : h->up)
-    if (p.mode == VF_IMAGES) p.mode = VF_TRACKS;  // what the pair is once its points are tracked
+    if (p.mode == VF_IMAGES || p.mode == VF_DETECT) p.mode = VF_TRACKS;  // once its points are tracked
   LOAM_HIP(hipMemcpyAsync(h->d_pairs, h->up.data(), sizeof(VfPair) * P, hipMemcpyHostToDevice, st));
   LOAM_HIP(hipMemcpyAsync(h->d_x, h->x0.data(), sizeof(double) * 6 * P, hipMemcpyHostToDevice, st));
   if (images) LOAM_HIP(hipMemcpyAsync(h->d_lk, h->lk_in.data(), sizeof(LkPair) * P, hipMemcpyHostToDevice, st));
+  if (detect)
+    LOAM_HIP(hipMemcpyAsync(h->gfb.gf, h->gf_in.data(), sizeof(GfPair) * P, hipMemcpyHostToDevice, st));
   LOAM_HIP(hipEventRecord(h->ev[0], st));
+  if (detect)  // after the tables' upload: it writes the corner counts into them
+    TRY(gftt_launch(h->gf, h->gfb, h->gf_in.data(), P, h->d_pyr, h->lk.image_bytes, h->d_kp0, K, h->d_pairs, h->d_lk,
+                    st));
   if (images)
     TRY(lk_launch(h->lk, h->d_lk, h->lk_in.data(), P, h->d_pyr, h->d_kp0, h->d_kp1, h->d_status, h->d_err, K, st));
   if (match) {
@@ -658,6 +756,8 @@ int32_t loam_vo_frames_solve(loam_vo_frames* h) {
   LOAM_HIP(hipMemcpyAsync(x.data(), h->d_x, sizeof(double) * 6 * P, hipMemcpyDeviceToHost, st));
   LOAM_HIP(hipMemcpyAsync(lm.data(), h->d_lm, sizeof(loam_lm_stats) * P, hipMemcpyDeviceToHost, st));
   LOAM_HIP(hipMemcpyAsync(cnt.data(), h->d_cnt, sizeof(VfCount) * P, hipMemcpyDeviceToHost, st));
+  std::vector<GfState> gfs(detect ? P : 0);
+  if (detect) LOAM_HIP(hipMemcpyAsync(gfs.data(), h->gfb.state, sizeof(GfState) * P, hipMemcpyDeviceToHost, st));
   LOAM_HIP(hipStreamSynchronize(st));
   LOAM_HIP(hipEventElapsedTime(&h->ms, h->ev[0], h->ev[1]));
   for (int p = 0; p < P; ++p) {
@@ -667,11 +767,17 @@ int32_t loam_vo_frames_solve(loam_vo_frames* h) {
     h->cnt[p] = cnt[p];
     h->solved[p] = 1;
     const int mode = h->pairs[p].mode;
-    h->tracks_n[p] = mode == VF_DESC ? -1 : h->pairs[p].n0;
+    h->tracks_n[p] = mode == VF_DESC ? -1 : mode == VF_DETECT ? gfs[p].n_corners : h->pairs[p].n0;
     h->tracks_mode[p] = mode;
-    if (mode == VF_IMAGES) {
+    h->gf_state[p] = mode == VF_DETECT ? gfs[p] : GfState{};
+    if (mode == VF_IMAGES || mode == VF_DETECT) {
       h->lk_done[p] = h->lk_in[p];
+      h->lk_done[p].n = h->tracks_n[p];
       h->lk_in[p].active = 0;
+    }
+    if (mode == VF_DETECT) {
+      h->gf_done[p] = h->gf_in[p];
+      h->gf_in[p].active = 0;
     }
     h->pairs[p].mode = VF_NONE;
   }
@@ -684,6 +790,16 @@ int32_t loam_vo_frames_result(loam_vo_frames* h, int32_t pair, double* x6, loam_
   if (!h->solved[pair]) {
     set_error("loam_vo_frames_result: the pair was never solved");
     return LOAM_ERR_STATE;
+  }
+  const GfState& g = h->gf_state[pair];
+  if (g.n_cand > h->gf.max_cand && h->gf_on) {
+    set_error("loam_vo_frames_result: the image has " + std::to_string(g.n_cand) +
+              " corner candidates, more than max_candidates = " + std::to_string(h->gf.max_cand));
+    return LOAM_ERR_CAPACITY;
+  }
+  if (g.err) {
+    set_error("loam_vo_frames_result: a cell of the corner grid was full");
+    return LOAM_ERR_CAPACITY;
   }
   if (x6)
     for (int i = 0; i < 6; ++i) x6[i] = h->x[(size_t)pair * 6 + i];
@@ -745,7 +861,7 @@ int32_t loam_vo_frames_tracks_copy(loam_vo_frames* h, int32_t pair, float* prev_
   if (curr_xy) LOAM_HIP(hipMemcpy(curr_xy, h->d_kp1 + o, sizeof(float2) * n, hipMemcpyDeviceToHost));
   if (status) LOAM_HIP(hipMemcpy(status, h->d_status + o, (size_t)n, hipMemcpyDeviceToHost));
   if (err) {
-    if (h->tracks_mode[pair] == VF_IMAGES)
+    if (h->tracks_mode[pair] == VF_IMAGES || h->tracks_mode[pair] == VF_DETECT)
       LOAM_HIP(hipMemcpy(err, h->d_err + o, sizeof(float) * n, hipMemcpyDeviceToHost));
     else
       std::fill(err, err + n, 0.f);
@@ -779,6 +895,24 @@ int32_t loam_vo_frames_pyramid_copy(loam_vo_frames* h, int32_t pair, int32_t ima
   LOAM_HIP(hipSetDevice(h->dev));
   LOAM_HIP(hipMemcpy(out, h->d_pyr + ((size_t)pair * 2 + image) * h->lk.image_bytes + h->lk.lvl_off[level], (size_t)n,
                      hipMemcpyDeviceToHost));
+  return n;
+}
+
+int32_t loam_vo_frames_eig_copy(loam_vo_frames* h, int32_t pair, float* out, int32_t cap, int32_t* wh) {
+  TRY(vf_check(h, pair, "loam_vo_frames_eig_copy"));
+  if (!h->gf_on || !h->gf_done[pair].active) {
+    set_error("loam_vo_frames_eig_copy: the pair has no solved detection (or a later input replaced it)");
+    return LOAM_ERR_STATE;
+  }
+  const GfPair& G = h->gf_done[pair];
+  if (wh) {
+    wh[0] = G.w;
+    wh[1] = G.h;
+  }
+  const int n = G.w * G.h;
+  if (n > cap || !out) return n;  // the size only
+  LOAM_HIP(hipSetDevice(h->dev));
+  LOAM_HIP(hipMemcpy(out, h->gfb.eig + (size_t)pair * h->gf.eig_stride, sizeof(float) * n, hipMemcpyDeviceToHost));
   return n;
 }
 

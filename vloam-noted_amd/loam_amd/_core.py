@@ -70,6 +70,11 @@ class LKParams(ctypes.Structure):
                 ("max_count", c_i32), ("epsilon", c_d), ("min_eig_threshold", c_d)]
 
 
+class GFTTParams(ctypes.Structure):
+    _fields_ = [("max_corners", c_i32), ("quality_level", c_d), ("min_distance", c_d), ("block_size", c_i32),
+                ("max_candidates", c_i32)]
+
+
 class VOFrameStats(ctypes.Structure):
     _fields_ = [("n_knn", c_i32), ("n_matches", c_i32), ("n_gated", c_i32), ("counter32", c_i32),
                 ("counter22", c_i32), ("ms", c_d)]
@@ -186,6 +191,10 @@ SIGNATURES = {
     "loam_vo_frames_input_images": (c_i32, [vp, c_i32, vp, vp, c_i32, c_i32, c_i32, vp, c_i32, c_i32]),
     "loam_vo_frames_tracks_copy": (c_i32, [vp, c_i32, vp, vp, vp, vp, c_i32]),
     "loam_vo_frames_pyramid_copy": (c_i32, [vp, c_i32, c_i32, c_i32, vp, c_i32, vp]),
+    "loam_gftt_params_default": (None, [ctypes.POINTER(GFTTParams)]),
+    "loam_vo_frames_enable_detection": (c_i32, [vp, ctypes.POINTER(GFTTParams)]),
+    "loam_vo_frames_input_image_pair": (c_i32, [vp, c_i32, vp, vp, c_i32, c_i32, c_i32, c_i32, c_i32]),
+    "loam_vo_frames_eig_copy": (c_i32, [vp, c_i32, vp, c_i32, vp]),
     "loam_lm_solve": (c_i32, [c_i32, vp, c_i32, vp, c_i32, ctypes.POINTER(LMStats)]),
     "loam_lm_normal_equations": (c_i32, [c_i32, vp, c_i32, vp, vp, vp, vp]),
     "loam_voxel_grid": (c_i32, [c_i32, vp, c_i32, c_f, vp, ctypes.POINTER(c_i32)]),

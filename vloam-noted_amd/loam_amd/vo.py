@@ -96,6 +96,16 @@ def lk_params(max_width, max_height, **kw):
     return p
 
 
+def gftt_params(**kw):
+    """loam_gftt_params: the reference's cv::goodFeaturesToTrack call (1024 corners, quality 0.03,
+    minDistance 7.5, blockSize 5), 65536 candidates per image"""
+    p = _core.GFTTParams()
+    lib().loam_gftt_params_default(ctypes.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
 class VOFrames:
     """The VO frame on the device (loam_vo_frames_*): ``n_pairs`` independent frame pairs, each
     from its descriptors (or LK tracks) to angles_0to1 / t_0to1 in one launch sequence per
@@ -162,6 +172,33 @@ class VOFrames:
         check(lib().loam_vo_frames_input_images(self.h, pair, a.ctypes.data, b.ctypes.data, w, h,
                                                 a.strides[0] if a.size else w, ptr(pts), len(pts),
                                                 depth_stream_prev))
+
+    def enable_detection(self, **kw):
+        """allocate the corner detector's buffers of every pair (once, after enable_images); kw:
+        loam_gftt_params fields"""
+        self.gftt = gftt_params(**kw)
+        check(lib().loam_vo_frames_enable_detection(self.h, ctypes.byref(self.gftt)))
+
+    def input_image_pair(self, pair, img_prev, img_curr, detect_on=0, depth_stream_prev=0):
+        """optical_flow_match from the two images alone: goodFeaturesToTrack on the previous image
+        (detect_on 0) or the current one (1, the reference's order) runs on the device, and the
+        corners are tracked from img_prev to img_curr"""
+        a, b = np.asarray(img_prev), np.asarray(img_curr)
+        if a.dtype != np.uint8 or b.dtype != np.uint8 or a.ndim != 2 or a.shape != b.shape:
+            raise ValueError("two 8-bit single-channel images of one size")
+        if a.size and (a.strides[1] != 1 or b.strides != a.strides):
+            a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+        h, w = a.shape
+        check(lib().loam_vo_frames_input_image_pair(self.h, pair, a.ctypes.data, b.ctypes.data, w, h,
+                                                    a.strides[0] if a.size else w, detect_on, depth_stream_prev))
+
+    def eig(self, pair=0):
+        """the (h, w) float32 minimum-eigenvalue plane of the pair's last detection"""
+        wh = np.zeros(2, np.int32)
+        n = check(lib().loam_vo_frames_eig_copy(self.h, pair, None, 0, ptr(wh)))
+        out = np.empty((int(wh[1]), int(wh[0])), np.float32)
+        check(lib().loam_vo_frames_eig_copy(self.h, pair, ptr(out), n, None))
+        return out
 
     def set_initial(self, pair, x6=None):
         x = None if x6 is None else np.ascontiguousarray(x6, dtype=np.float64).reshape(6)
