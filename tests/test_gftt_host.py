@@ -5,7 +5,6 @@ selection against its defining properties and against a restatement of OpenCV's 
 order of planted ties; then the argument checks of the new entry points that need no device, and
 that the C++ shim's detection path compiles as the nodes compile it."""
 import ctypes
-import os
 import subprocess
 
 import numpy as np
@@ -14,8 +13,8 @@ from scipy import ndimage
 
 import gftt_np as G
 import lk_np as L
-from conftest import ROOT
 from loam_amd import _core, vo
+from vo_frames_util import compile_shim
 
 SIZES = [(16, 17), (31, 33), (65, 97), (2, 9), (9, 1)]  # (height, width)
 
@@ -183,14 +182,9 @@ def test_entry_points_validate_before_any_device_work():
 
 
 def test_cxx_detect_check_compiles(tmp_path):
-    """tests/cxx/vo_detect_check.cpp through include/loam_core.hpp with the nodes' compiler and
+    """tests/cxx/vo_frames_check.cpp through include/loam_core.hpp with the nodes' compiler and
     warnings; without an input file it only reports the library version"""
-    lib_dir = os.path.dirname(_core.LIB_PATH)
-    exe = str(tmp_path / "vo_detect_check")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "tests", "cxx", "vo_detect_check.cpp"), "-o", exe, "-L", lib_dir,
-                    "-lloam_core", f"-Wl,-rpath,{lib_dir}", "-Wl,-rpath,/opt/rocm/lib"],
-                   check=True, capture_output=True, text=True)
+    exe = compile_shim(tmp_path)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "version" in r.stdout

@@ -13,43 +13,20 @@ cv::goodFeaturesToTrack (tests/gftt_np.py), bit for bit.
 The counts of candidates, corners and ties asserted here are the committed model's own on these
 inputs: a drifting input is noticed."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import gftt_np as G
 import lk_np as L
-from conftest import ROOT
-from loam_amd import _core, synth, vo
-from loam_amd.depth import KITTI_CAM_T_VELO, KITTI_P_RECT0, KITTI_RECT0_T_CAM, BatchDepth
+from loam_amd import _core, vo
+from vo_frames_util import X_INIT, counters, give, make_depth, raises, run_shim, same_bits, same_lm, strided
 
 pytestmark = pytest.mark.gpu
 
-X_INIT = np.array([0.008, -0.018, 0.004, 0.04, -0.01, -0.85])
-
-
 @pytest.fixture(scope="module")
 def depth():
-    clouds = [synth.frame(21, 4 + s, 800)[0] for s in range(2)]
-    g = BatchDepth(2)
-    for s, c in enumerate(clouds):
-        g.input(s, c)
-    g.process()
-    return g, clouds
-
-
-def strided(img, extra=13):
-    """the same image as a view of rows that are `extra` bytes longer"""
-    buf = np.full((img.shape[0], img.shape[1] + extra), 0xA5, np.uint8)
-    buf[:, :img.shape[1]] = img
-    return buf[:, :img.shape[1]]
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
+    return make_depth()
 
 
 def noise(w, h):
@@ -192,15 +169,6 @@ def test_kitti_size_noise(depth):
 
 
 # ---------------------------------------------------------------------------------------- 4
-def same_lm(a, b):
-    return [a.iterations, a.successful, a.invalid, a.termination, a.initial_cost, a.final_cost] == \
-        [b.iterations, b.successful, b.invalid, b.termination, b.initial_cost, b.final_cost]
-
-
-def counters(s):
-    return [s.n_knn, s.n_matches, s.n_gated, s.counter32, s.counter22]
-
-
 def assert_same_frame(a, pa, b, pb):
     (xa, la, sa), (xb, lb, sb) = a.result(pa), b.result(pb)
     assert same_bits(xa, xb) and same_lm(la, lb) and counters(sa) == counters(sb)
@@ -244,12 +212,6 @@ def test_fused_frame_equals_images_of_the_models_corners(depth, kitti_pair, dete
 
 
 # ---------------------------------------------------------------------------------------- 5
-def give(vf, pair, item):
-    kind, data, stream, x0 = item
-    getattr(vf, "input_" + kind)(pair, *data, stream)
-    vf.set_initial(pair, x0)
-
-
 def test_batch_equals_single_pairs(depth, kitti_pair):
     g, _ = depth
     rng = np.random.default_rng(12)
@@ -302,13 +264,6 @@ def test_batch_equals_single_pairs(depth, kitti_pair):
 
 
 # ---------------------------------------------------------------------------------------- 6
-def raises(rc, fn, *a, **kw):
-    with pytest.raises(_core.LoamError) as e:
-        fn(*a, **kw)
-    assert e.value.rc == rc, (e.value.rc, str(e.value))
-    return str(e.value)
-
-
 def test_candidate_overflow(depth):
     g, _ = depth
     img, ok = noise(128, 96), L.Scene(3).render(128, 96)
@@ -389,30 +344,8 @@ def test_cxx_shim_reproduces_python(depth, kitti_pair, tmp_path):
     vf.solve()
     x, lm, st = vf.result(0)
     tp, tc, ts, te = vf.tracks(0)
-    path = str(tmp_path / "pair.bin")
-    with open(path, "wb") as f:
-        f.write(np.array([len(clouds[0]), 1241, 376, 1248, 1], np.int32).tobytes())
-        for a in (KITTI_CAM_T_VELO, KITTI_RECT0_T_CAM, KITTI_P_RECT0):
-            f.write(np.ascontiguousarray(a, np.float32).tobytes())
-        f.write(X_INIT.astype(np.float64).tobytes())
-        f.write(np.ascontiguousarray(clouds[0]).tobytes())
-        for img in (prev, curr):
-            f.write(np.ascontiguousarray(strided(img, 7).base).tobytes())
-    lib_dir = os.path.dirname(_core.LIB_PATH)
-    exe = str(tmp_path / "vo_detect_check")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "tests", "cxx", "vo_detect_check.cpp"), "-o", exe, "-L", lib_dir,
-                    "-lloam_core", f"-Wl,-rpath,{lib_dir}", "-Wl,-rpath,/opt/rocm/lib"],
-                   check=True, capture_output=True, text=True)
-    r = subprocess.run([exe, path], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stdout + r.stderr
-    lines, got_t = {}, []
-    for line in r.stdout.splitlines():
-        key, *vals = line.split()
-        if key == "t":
-            got_t.append(vals)
-        else:
-            lines[key] = vals
+    lines, got_t = run_shim(tmp_path, "detect", [len(clouds[0]), 1241, 376, 1248, 1],
+                            [clouds[0], strided(prev, 7).base, strided(curr, 7).base])
     assert [float.fromhex(v) for v in lines["x"]] == x.tolist()
     assert [int(v) for v in lines["lm"][:4]] == [lm.iterations, lm.successful, lm.invalid, lm.termination]
     assert [float.fromhex(v) for v in lines["lm"][4:]] == [lm.initial_cost, lm.final_cost]

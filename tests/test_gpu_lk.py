@@ -14,40 +14,22 @@ cv::calcOpticalFlowPyrLK (tests/lk_np.py), bit for bit.
     counters and records, bit for bit;
  5. batch: five pairs of all three modes in one handle equal their single-pair calls;
  6. errors; 7. the C++ shim reproduces the Python tracks and pose bit for bit."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import lk_np as L
-from conftest import ROOT
-from loam_amd import _core, synth, vo
-from loam_amd.depth import KITTI_CAM_T_VELO, KITTI_P_RECT0, KITTI_RECT0_T_CAM, BatchDepth
+from loam_amd import _core, vo
+from vo_frames_util import X_INIT, counters, give, make_depth, raises, run_shim, same_bits, same_lm, strided
 
 pytestmark = pytest.mark.gpu
 
 W, H = 97, 65
 NS = (0, 1, 63, 64, 65, 257)
-X_INIT = np.array([0.008, -0.018, 0.004, 0.04, -0.01, -0.85])
 
 
 @pytest.fixture(scope="module")
 def depth():
-    """two processed depth streams (consecutive synthetic frames) and their clouds"""
-    clouds = [synth.frame(21, 4 + s, 800)[0] for s in range(2)]
-    g = BatchDepth(2)
-    for s, c in enumerate(clouds):
-        g.input(s, c)
-    g.process()
-    return g, clouds
-
-
-def strided(img, extra=13):
-    """the same image as a view of rows that are `extra` bytes longer"""
-    buf = np.full((img.shape[0], img.shape[1] + extra), 0xA5, np.uint8)
-    buf[:, :img.shape[1]] = img
-    return buf[:, :img.shape[1]]
+    return make_depth()
 
 
 def planted_points(rng, w, h, flat, n):
@@ -65,11 +47,6 @@ def planted_points(rng, w, h, flat, n):
     pts = np.concatenate([np.array(special), np.stack([gx.ravel(), gy.ravel()], axis=1)])
     more = np.stack([rng.uniform(-10, w + 10, n), rng.uniform(-10, h + 10, n)], axis=1)
     return np.concatenate([pts, more])[:n].astype(np.float32)
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
 
 
 def device_tracks(g, prev, curr, pts, stream=0, **lk):
@@ -193,15 +170,6 @@ def kitti_pair():
     return prev, curr, pts, L.track(prev, curr, pts)
 
 
-def same_lm(a, b):
-    return [a.iterations, a.successful, a.invalid, a.termination, a.initial_cost, a.final_cost] == \
-        [b.iterations, b.successful, b.invalid, b.termination, b.initial_cost, b.final_cost]
-
-
-def counters(s):
-    return [s.n_knn, s.n_matches, s.n_gated, s.counter32, s.counter22]
-
-
 def assert_same_frame(a, pa, b, pb):
     (xa, la, sa), (xb, lb, sb) = a.result(pa), b.result(pb)
     assert same_bits(xa, xb) and same_lm(la, lb) and counters(sa) == counters(sb)
@@ -236,12 +204,6 @@ def test_fused_frame_equals_tracks_of_the_model(depth, kitti_pair, x0):
 
 
 # ---------------------------------------------------------------------------------------- 5
-def give(vf, pair, item):
-    kind, data, stream, x0 = item
-    getattr(vf, "input_" + kind)(pair, *data, stream)
-    vf.set_initial(pair, x0)
-
-
 def test_batch_equals_single_pairs(depth, small, kitti_pair):
     g, _ = depth
     rng = np.random.default_rng(12)
@@ -292,12 +254,6 @@ def test_batch_equals_single_pairs(depth, small, kitti_pair):
 
 
 # ---------------------------------------------------------------------------------------- 6
-def raises(rc, fn, *a, **kw):
-    with pytest.raises(_core.LoamError) as e:
-        fn(*a, **kw)
-    assert e.value.rc == rc, (e.value.rc, str(e.value))
-
-
 def test_errors(depth, small):
     g, _ = depth
     prev, curr, pts, _, _ = small
@@ -350,31 +306,8 @@ def test_cxx_shim_reproduces_python(depth, kitti_pair, tmp_path):
     vf.solve()
     x, lm, st = vf.result(0)
     tp, tc, ts, te = vf.tracks(0)
-    path = str(tmp_path / "pair.bin")
-    with open(path, "wb") as f:
-        f.write(np.array([len(clouds[0]), 1241, 376, 1248, len(pts)], np.int32).tobytes())
-        for a in (KITTI_CAM_T_VELO, KITTI_RECT0_T_CAM, KITTI_P_RECT0):
-            f.write(np.ascontiguousarray(a, np.float32).tobytes())
-        f.write(X_INIT.astype(np.float64).tobytes())
-        f.write(np.ascontiguousarray(clouds[0]).tobytes())
-        for img in (prev, curr):
-            f.write(np.ascontiguousarray(strided(img, 7).base).tobytes())
-        f.write(pts.tobytes())
-    lib_dir = os.path.dirname(_core.LIB_PATH)
-    exe = str(tmp_path / "vo_images_check")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "tests", "cxx", "vo_images_check.cpp"), "-o", exe, "-L", lib_dir,
-                    "-lloam_core", f"-Wl,-rpath,{lib_dir}", "-Wl,-rpath,/opt/rocm/lib"],
-                   check=True, capture_output=True, text=True)
-    r = subprocess.run([exe, path], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stdout + r.stderr
-    lines, got_t = {}, []
-    for line in r.stdout.splitlines():
-        key, *vals = line.split()
-        if key == "t":
-            got_t.append(vals)
-        else:
-            lines[key] = vals
+    lines, got_t = run_shim(tmp_path, "images", [len(clouds[0]), 1241, 376, 1248, len(pts)],
+                            [clouds[0], strided(prev, 7).base, strided(curr, 7).base, pts])
     assert [float.fromhex(v) for v in lines["x"]] == x.tolist()
     assert [int(v) for v in lines["lm"][:4]] == [lm.iterations, lm.successful, lm.invalid, lm.termination]
     assert [float.fromhex(v) for v in lines["lm"][4:]] == [lm.initial_cost, lm.final_cost]

@@ -12,35 +12,25 @@ tracks in, angles_0to1 / t_0to1 out.
     through vo.solve to the fused call's x bit for bit;
  4. batch: five pairs in one handle equal their single-pair calls bit for bit;
  5. errors; 6. the C++ shim reproduces the Python result bit for bit."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import loam_oracle as O
 import vo_frames_np as N
-from conftest import ROOT
-from loam_amd import _core, synth, vo
+from loam_amd import _core, vo
 from loam_amd.depth import KITTI_CAM_T_VELO, KITTI_P_RECT0, KITTI_RECT0_T_CAM, BatchDepth
 from scipy.spatial.transform import Rotation
+from vo_frames_util import X_INIT, give, make_depth, run_shim
 
 pytestmark = pytest.mark.gpu
 
 # a camera matrix with skew, unequal focal lengths and a tilted last row: the LU pivots
 K_SKEW = np.array([[718.3, 1.7, 607.2, 0.0], [-0.9, 722.6, 185.2, 0.0], [1.5e-3, -2.5e-3, 1.0, 0.0]], np.float32)
-X_INIT = np.array([0.008, -0.018, 0.004, 0.04, -0.01, -0.85])
 
 
 @pytest.fixture(scope="module")
 def scene():
-    """two processed depth streams (consecutive synthetic frames) and their clouds"""
-    clouds = [synth.frame(21, 4 + s, 800)[0] for s in range(2)]
-    g = BatchDepth(2)
-    for s, c in enumerate(clouds):
-        g.input(s, c)
-    g.process()
-    return g, clouds
+    return make_depth()
 
 
 def same_lm(a, b):
@@ -231,23 +221,14 @@ def matched_pair(rng, n0, n1, nb=32):
     return kp0, d0, kp1, d1
 
 
-def give(vf, pair, item):
-    kind, data, stream, x0 = item
-    if kind == "desc":
-        vf.input_descriptors(pair, *data, stream)
-    else:
-        vf.input_tracks(pair, *data, stream)
-    vf.set_initial(pair, x0)
-
-
 def test_batch_equals_single_pairs(scene):
     g, _ = scene
     rng = np.random.default_rng(12)
-    items = [("desc", matched_pair(rng, 300, 400), 0, None),
-             ("desc", matched_pair(rng, 0, 50), 1, np.full(6, 0.5)),        # the empty pair
-             ("desc", matched_pair(rng, 1000, 900), 1, X_INIT),
+    items = [("descriptors", matched_pair(rng, 300, 400), 0, None),
+             ("descriptors", matched_pair(rng, 0, 50), 1, np.full(6, 0.5)),        # the empty pair
+             ("descriptors", matched_pair(rng, 1000, 900), 1, X_INIT),
              ("tracks", planted_tracks(rng, 500), 0, None),
-             ("desc", matched_pair(rng, 257, 64), 0, 0.5 * X_INIT)]
+             ("descriptors", matched_pair(rng, 257, 64), 0, 0.5 * X_INIT)]
     batch = vo.VOFrames(g, len(items))
     for p, item in enumerate(items):
         give(batch, p, item)
@@ -320,6 +301,40 @@ def test_errors(scene):
     half.close()
 
 
+def test_results_survive_a_later_input(scene):
+    """result, matches and records are the last solve's until the next solve; the tracks are gone
+    with the first later input"""
+    g, _ = scene
+    rng = np.random.default_rng(8)
+    d0 = rng.integers(0, 256, (9, 32), dtype=np.uint8)
+    d1 = rng.integers(0, 256, (8, 32), dtype=np.uint8)
+    d1[:6] = d0[:6]
+    desc = (random_keypoints(rng, 9), d0, random_keypoints(rng, 8), d1)
+    prev = random_keypoints(rng, 10)
+    tracks = (prev, prev + rng.normal(0, 3, (10, 2)).astype(np.float32), np.ones(10, np.uint8))
+
+    def everything(vf, pair):
+        x, lm, st = vf.result(pair)
+        rec, dep = vf.records(pair)
+        return (x.tobytes(), [lm.iterations, lm.successful, lm.invalid, lm.termination, lm.initial_cost, lm.final_cost],
+                [st.n_knn, st.n_matches, st.n_gated, st.counter32, st.counter22], vf.matches(pair).tobytes(),
+                rec.tobytes(), dep.tobytes())
+
+    vf = vo.VOFrames(g, 2, max_keypoints=64)
+    vf.input_descriptors(0, *desc, 0)
+    vf.input_tracks(1, *tracks, 1)
+    vf.solve()
+    before = [everything(vf, p) for p in (0, 1)]
+    assert len(vf.matches(0)) >= 6 and len(vf.matches(1)) == 10 and len(vf.tracks(1)[2]) == 10
+    vf.input_tracks(0, *tracks, 0)
+    vf.input_descriptors(1, *desc, 1)
+    assert [everything(vf, p) for p in (0, 1)] == before
+    with pytest.raises(_core.LoamError) as e:
+        vf.tracks(1)
+    assert e.value.rc == -4                                  # LOAM_ERR_STATE: replaced by the later input
+    vf.close()
+
+
 # ---------------------------------------------------------------------------------------- 6
 def test_cxx_shim_reproduces_python(scene, tmp_path):
     g, clouds = scene
@@ -332,30 +347,9 @@ def test_cxx_shim_reproduces_python(scene, tmp_path):
     vf.solve()
     x, lm, st = vf.result(0)
     m = vf.matches(0)
-    path = str(tmp_path / "pair.bin")
-    with open(path, "wb") as f:
-        f.write(np.array([len(clouds[0]), len(kp0), len(kp1), 32], np.int32).tobytes())
-        for a in (KITTI_CAM_T_VELO, KITTI_RECT0_T_CAM, KITTI_P_RECT0):
-            f.write(np.ascontiguousarray(a, np.float32).tobytes())
-        f.write(X_INIT.astype(np.float64).tobytes())
-        for a in (clouds[0], kp0, d0, kp1, d1):
-            f.write(np.ascontiguousarray(a).tobytes())
-    lib_dir = os.path.dirname(_core.LIB_PATH)
-    exe = str(tmp_path / "vo_frames_check")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "tests", "cxx", "vo_frames_check.cpp"), "-o", exe, "-L", lib_dir,
-                    "-lloam_core", f"-Wl,-rpath,{lib_dir}", "-Wl,-rpath,/opt/rocm/lib"],
-                   check=True, capture_output=True, text=True)
-    r = subprocess.run([exe, path], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stdout + r.stderr
-    lines = {}
-    got_m = []
-    for line in r.stdout.splitlines():
-        key, *vals = line.split()
-        if key == "m":
-            got_m.append([int(v) for v in vals])
-        else:
-            lines[key] = vals
+    lines, got_m = run_shim(tmp_path, "descriptors", [len(clouds[0]), len(kp0), len(kp1), 32],
+                            [clouds[0], kp0, d0, kp1, d1])
+    got_m = [[int(v) for v in vals] for vals in got_m]
     assert [float.fromhex(v) for v in lines["x"]] == x.tolist()
     assert [int(v) for v in lines["lm"][:4]] == [lm.iterations, lm.successful, lm.invalid, lm.termination]
     assert [float.fromhex(v) for v in lines["lm"][4:]] == [lm.initial_cost, lm.final_cost]

@@ -5,7 +5,6 @@ motion of a synthetic scene, the flat patch and the points far outside; then the
 of the new entry points that need no device, and that the C++ shim's images path compiles as the
 nodes compile it."""
 import ctypes
-import os
 import subprocess
 
 import numpy as np
@@ -13,8 +12,8 @@ import pytest
 from scipy import ndimage
 
 import lk_np as L
-from conftest import ROOT
 from loam_amd import _core, vo
+from vo_frames_util import compile_shim
 
 SIZES = [(16, 17), (17, 16), (31, 33), (48, 64), (65, 97), (2, 9)]  # (height, width)
 
@@ -154,14 +153,9 @@ def test_entry_points_validate_before_any_device_work():
 
 
 def test_cxx_images_check_compiles(tmp_path):
-    """tests/cxx/vo_images_check.cpp through include/loam_core.hpp with the nodes' compiler and
+    """tests/cxx/vo_frames_check.cpp through include/loam_core.hpp with the nodes' compiler and
     warnings; without an input file it only reports the library version"""
-    lib_dir = os.path.dirname(_core.LIB_PATH)
-    exe = str(tmp_path / "vo_images_check")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "tests", "cxx", "vo_images_check.cpp"), "-o", exe, "-L", lib_dir,
-                    "-lloam_core", f"-Wl,-rpath,{lib_dir}", "-Wl,-rpath,/opt/rocm/lib"],
-                   check=True, capture_output=True, text=True)
+    exe = compile_shim(tmp_path)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "version" in r.stdout

@@ -3,7 +3,6 @@ tests compare against agrees with a second formulation on the planted cases, the
 are what they claim, vo_to_velo_prior against a plain 4x4 composition, the argument checks that
 need no device, and that the C++ shim's VisualOdometryFrames compiles as the nodes compile it."""
 import ctypes
-import os
 import subprocess
 
 import numpy as np
@@ -11,8 +10,8 @@ import pytest
 from scipy.spatial.transform import Rotation
 
 import vo_frames_np as N
-from conftest import ROOT
 from loam_amd import _core, vo
+from vo_frames_util import compile_shim
 
 
 @pytest.mark.parametrize("n0,n1,nb", [(257, 300, 32), (65, 64, 64), (40, 3, 32), (5, 2, 8), (3, 1, 32), (0, 70, 32),
@@ -118,12 +117,7 @@ def test_entry_points_validate_before_any_device_work():
 def test_cxx_shim_check_compiles(tmp_path):
     """tests/cxx/vo_frames_check.cpp through include/loam_core.hpp with the nodes' compiler and
     warnings; without an input file it only reports the library version"""
-    lib_dir = os.path.dirname(_core.LIB_PATH)
-    exe = str(tmp_path / "vo_frames_check")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "tests", "cxx", "vo_frames_check.cpp"), "-o", exe, "-L", lib_dir,
-                    "-lloam_core", f"-Wl,-rpath,{lib_dir}", "-Wl,-rpath,/opt/rocm/lib"],
-                   check=True, capture_output=True, text=True)
+    exe = compile_shim(tmp_path)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "version" in r.stdout

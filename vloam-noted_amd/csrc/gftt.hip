@@ -374,3 +374,13 @@ int32_t gftt_launch(const GfPlan& plan, const GfBuffers& B, const GfPair* pairs,
 }
 
 }  // namespace loam
+
+extern "C" void loam_gftt_params_default(loam_gftt_params* p) {
+  if (!p) return;
+  *p = loam_gftt_params{};
+  p->max_corners = 1024;
+  p->quality_level = 0.03;
+  p->min_distance = 7.5;
+  p->block_size = 5;
+  p->max_candidates = 65536;
+}

@@ -1,20 +1,10 @@
-// gftt_dev.h — Shi-Tomasi corner detection on an image that is already in device memory (gftt.hip),
-// and the pair table the frame kernels share with it.
+// gftt_dev.h — Shi-Tomasi corner detection on an image that is already in device memory (gftt.hip).
 #pragma once
 #include "common.h"
 #include "lk_dev.h"
+#include "vo_frames_dev.h"
 
 namespace loam {
-
-enum { VF_NONE = 0, VF_DESC = 1, VF_TRACKS = 2, VF_IMAGES = 3, VF_DETECT = 4 };
-
-// one frame pair as the frame kernels see it (VF_IMAGES / VF_DETECT are the host's: the kernels are
-// handed such a pair as VF_TRACKS)
-struct VfPair {
-  int mode;    // VF_*: what the pair's pending input is
-  int n0, n1;  // descriptors of image 0 / 1 (tracks: n0 = n1 = n)
-  int stream;  // depth stream of the previous frame
-};
 
 constexpr int GF_MAX_BLOCK = 15;
 constexpr int GF_MAX_DIM = 65535;          // a kept corner is packed as x | y << 16

@@ -356,3 +356,13 @@ int32_t lk_launch(const LkPlan& plan, const LkPair* d_pairs, const LkPair* pairs
 }
 
 }  // namespace loam
+
+extern "C" void loam_lk_params_default(loam_lk_params* p) {
+  if (!p) return;
+  *p = loam_lk_params{};
+  p->win = 15;
+  p->max_level = 2;
+  p->max_count = 10;
+  p->epsilon = 0.03;
+  p->min_eig_threshold = 1e-4;
+}

@@ -27,6 +27,9 @@
 // (loam_vo_frames_input_image_pair) runs gftt.hip's corner detection in front of that: it leaves kp0
 // and, on the device, the point count in the pair tables the tracker and the kernels here read.
 // No workgroup waits on another: the merge is a launch of its own.
+// Host: one VfHost per pair.  loam_vo_frames_solve plans (the stages to run and the kernels' tables,
+// from the pending inputs), enqueues (one launch sequence) and collects (the read-back; the pending
+// inputs become last solves).
 //
 // Records: the right-hand sides are formed in float as the reference does, the 3 x 3 solve with
 // K = P_rect0.leftCols(3) runs in fp64 (an LU with partial pivoting, factored once on the host),
@@ -42,6 +45,7 @@
 #include "gftt_dev.h"
 #include "lk_dev.h"
 #include "vo_dev.h"
+#include "vo_frames_dev.h"
 
 namespace loam {
 
@@ -283,6 +287,28 @@ __global__ void __launch_bounds__(VA_THREADS) k_vo_assemble(const VfPair* pairs,
 
 using namespace loam;
 
+// One pair on the host.  in: the input that waits for the next solve (mode VF_NONE: none; VF_DETECT:
+// the counts are the device's).  done: what the last solve left (mode VF_NONE: never solved).
+struct VfImage {
+  int w, h, levels;  // level 0 of both images, the levels of their pyramids (VF_IMAGES / VF_DETECT)
+};
+struct VfInput {
+  VfPair pair;
+  VfImage img;
+  int detect_on;
+};
+struct VfDone {
+  int mode;
+  int n_tracks;   // points in d_kp0 / d_kp1 / d_status (0 for VF_DESC)
+  VfImage img;
+  GfState gf;     // zero unless VF_DETECT
+  bool replaced;  // a later input has overwritten the keypoints, pyramids and eigenvalue plane
+};
+struct VfHost {
+  VfInput in;
+  VfDone done;
+};
+
 struct loam_vo_frames {
   DevStream st;  // first: destroyed after everything below
   int dev = 0;
@@ -292,11 +318,13 @@ struct loam_vo_frames {
   loam_vo_frames_params prm{};
   loam_depth* depth = nullptr;
   VfCam cam{};
-  std::vector<VfPair> pairs;    // pending inputs
-  std::vector<char> solved;     // the pair has results
+  std::vector<VfHost> rec;      // [P]
   std::vector<double> x0, x;    // [P][6] initial values / results
   std::vector<loam_lm_stats> lm;
   std::vector<VfCount> cnt;
+  std::vector<VfPair> up;       // a solve's tables, from rec[].in; they outlive the asynchronous uploads
+  std::vector<LkPair> lk_up;
+  std::vector<GfPair> gf_up;
   DevPool pool;
   VfPair* d_pairs = nullptr;
   uint32_t *d_desc0 = nullptr, *d_desc1 = nullptr;  // [P][K][WP]
@@ -313,11 +341,6 @@ struct loam_vo_frames {
   // images mode (loam_vo_frames_enable_images)
   bool lk_on = false;
   LkPlan lk{};
-  std::vector<VfPair> up;        // pairs as the kernels see them
-  std::vector<LkPair> lk_in;     // the pending images inputs
-  std::vector<LkPair> lk_done;   // the images of the pair's last solve (active = 0: none, or replaced)
-  std::vector<int> tracks_n;     // points of the pair's last tracks / images solve; -1: none, or replaced
-  std::vector<int> tracks_mode;  // VF_TRACKS or VF_IMAGES
   uint8_t* d_pyr = nullptr;      // [P][2][lk.image_bytes]
   LkPair* d_lk = nullptr;        // [P]
   float* d_err = nullptr;        // [P][K]
@@ -325,9 +348,6 @@ struct loam_vo_frames {
   bool gf_on = false;
   GfPlan gf{};
   GfBuffers gfb{};
-  std::vector<GfPair> gf_in;     // the pending detect inputs
-  std::vector<GfPair> gf_done;   // the image of the pair's last detect solve (active = 0: none, or replaced)
-  std::vector<GfState> gf_state; // what the pair's last solve left (n_cand = 0 for the other modes)
   DevEvent ev[2];
   float ms = 0.f;
   ~loam_vo_frames() { (void)hipStreamSynchronize(st); }
@@ -387,19 +407,29 @@ int32_t vf_check_input(loam_vo_frames* h, int32_t pair, int32_t n0, int32_t n1, 
   return LOAM_OK;
 }
 
-// a new input: what the copies read of the pair's last solve is about to be overwritten
-void vf_replace(loam_vo_frames* h, int32_t pair) {
-  h->tracks_n[pair] = -1;
-  h->lk_done[pair].active = 0;
-  h->lk_in[pair].active = 0;
-  h->gf_done[pair].active = 0;
-  h->gf_in[pair].active = 0;
+// an accepted input: it has overwritten what the copies read of the pair's last solve
+void vf_replace(loam_vo_frames* h, int32_t pair, const VfInput& in) {
+  h->rec[pair].done.replaced = true;
+  h->rec[pair].in = in;
+}
+
+// the accessors' preamble: the pair's last solve, if it ran in min_mode or above (a mode leaves what
+// those below it leave; what those above VF_DESC add lies where a later input has written)
+int32_t vf_last(loam_vo_frames* h, int32_t pair, const char* who, int min_mode, const char* what,
+                const VfDone** out) {
+  TRY(vf_check(h, pair, who));
+  *out = &h->rec[pair].done;
+  if ((*out)->mode < min_mode || (min_mode > VF_DESC && (*out)->replaced)) {
+    set_error(std::string(who) + ": " + what);
+    return LOAM_ERR_STATE;
+  }
+  return LOAM_OK;
 }
 
 // the checks and the copies input_images and input_image_pair share: both images into level 0 of
 // the pair's pyramid slot
 int32_t vf_put_images(loam_vo_frames* h, int32_t pair, const uint8_t* img_prev, const uint8_t* img_curr,
-                      int32_t width, int32_t height, int32_t row_stride, const char* who) {
+                      int32_t width, int32_t height, int32_t row_stride, const char* who, VfImage* img) {
   if (!img_prev || !img_curr || width <= 0 || height <= 0 || row_stride < width) {
     set_error(std::string(who) + ": null input or bad image size");
     return LOAM_ERR_ARG;
@@ -413,6 +443,113 @@ int32_t vf_put_images(loam_vo_frames* h, int32_t pair, const uint8_t* img_prev, 
   LOAM_HIP(hipMemcpy2DAsync(lvl0, width, img_prev, row_stride, width, height, hipMemcpyHostToDevice, h->st));
   LOAM_HIP(hipMemcpy2DAsync(lvl0 + h->lk.image_bytes, width, img_curr, row_stride, width, height,
                             hipMemcpyHostToDevice, h->st));
+  *img = VfImage{width, height, lk_levels(width, height, h->lk.win, h->lk.max_level)};
+  return LOAM_OK;
+}
+
+struct VfStages {  // what a solve runs
+  bool match, images, detect;
+  int qb, S;  // the matcher's query blocks and slices of the train set
+};
+
+// the stages and the kernels' tables, from the pending inputs
+int32_t vf_plan(loam_vo_frames* h, VfStages* out) {
+  int active = 0, max_n0 = 0, max_n1 = 0;
+  VfStages g{};
+  for (int p = 0; p < h->P; ++p) {
+    const VfInput& in = h->rec[p].in;
+    const VfPair& q = in.pair;
+    const bool images = q.mode == VF_IMAGES || q.mode == VF_DETECT, detect = q.mode == VF_DETECT;
+    // an images / detect pair is a tracks pair once its points are tracked; a detect pair's n is the
+    // width of the tracker's grid until the detection writes the pair's own count over it
+    h->up[p] = VfPair{images ? VF_TRACKS : q.mode, q.n0, q.n1, q.stream};
+    h->lk_up[p] = LkPair{images, in.img.w, in.img.h, in.img.levels, detect ? h->gf.max_corners : q.n0};
+    h->gf_up[p] = GfPair{detect, in.img.w, in.img.h, in.detect_on};
+    if (q.mode == VF_NONE) continue;
+    ++active;
+    if (!depth_stream_processed(h->depth, q.stream)) {
+      set_error("loam_vo_frames_solve: depth stream " + std::to_string(q.stream) + " was never processed");
+      return LOAM_ERR_STATE;
+    }
+    g.images |= images;
+    g.detect |= detect;
+    if (q.mode == VF_DESC && q.n0 > 0 && q.n1 >= 2) {
+      g.match = true;
+      max_n0 = std::max(max_n0, q.n0);
+      max_n1 = std::max(max_n1, q.n1);
+    }
+  }
+  if (!active) {
+    set_error("loam_vo_frames_solve: no pair has an input");
+    return LOAM_ERR_STATE;
+  }
+  // slices of the train set: enough workgroups for two per CU, no slice thinner than a tile
+  const int qb = (max_n0 + VM_THREADS - 1) / VM_THREADS, tiles = (max_n1 + VM_TILE - 1) / VM_TILE;
+  int S = 1;
+  if (g.match) S = std::max(1, std::min({h->S_cap, tiles, (512 + qb * active - 1) / (qb * active)}));
+  *out = VfStages{g.match, g.images, g.detect, qb, S};
+  return LOAM_OK;
+}
+
+// the uploads and the launch sequence, between the handle's two events
+int32_t vf_enqueue(loam_vo_frames* h, const VfStages& g, const DepthDev& D) {
+  hipStream_t st = h->st;
+  const int P = h->P, K = h->K, S = g.S;
+  LOAM_HIP(hipMemcpyAsync(h->d_pairs, h->up.data(), sizeof(VfPair) * P, hipMemcpyHostToDevice, st));
+  LOAM_HIP(hipMemcpyAsync(h->d_x, h->x0.data(), sizeof(double) * 6 * P, hipMemcpyHostToDevice, st));
+  if (g.images) LOAM_HIP(hipMemcpyAsync(h->d_lk, h->lk_up.data(), sizeof(LkPair) * P, hipMemcpyHostToDevice, st));
+  if (g.detect)
+    LOAM_HIP(hipMemcpyAsync(h->gfb.gf, h->gf_up.data(), sizeof(GfPair) * P, hipMemcpyHostToDevice, st));
+  LOAM_HIP(hipEventRecord(h->ev[0], st));
+  if (g.detect)  // after the tables' upload: it writes the corner counts into them
+    TRY(gftt_launch(h->gf, h->gfb, h->gf_up.data(), P, h->d_pyr, h->lk.image_bytes, h->d_kp0, K, h->d_pairs, h->d_lk,
+                    st));
+  if (g.images)
+    TRY(lk_launch(h->lk, h->d_lk, h->lk_up.data(), P, h->d_pyr, h->d_kp0, h->d_kp1, h->d_status, h->d_err, K, st));
+  if (g.match) {
+    const dim3 grid(g.qb, S, P);
+    if (h->WP == 8)
+      k_vo_match<8><<<grid, VM_THREADS, 0, st>>>(h->d_pairs, h->d_desc0, h->d_desc1, K, S, h->d_part);
+    else
+      k_vo_match<16><<<grid, VM_THREADS, 0, st>>>(h->d_pairs, h->d_desc0, h->d_desc1, K, S, h->d_part);
+  }
+  k_vo_merge<<<P, VA_THREADS, 0, st>>>(h->d_pairs, h->d_part, S, K, h->prm.match_ratio, h->d_status, h->d_matches,
+                                       h->d_cnt);
+  k_vo_assemble<<<P, VA_THREADS, 0, st>>>(h->d_pairs, h->d_matches, h->d_cnt, h->d_kp0, h->d_kp1, K, D, h->cam,
+                                          h->prm.remove_vo_outlier, h->prm.depth_radius, h->d_records, h->d_depth0,
+                                          h->d_off);
+  LOAM_HIP(hipGetLastError());
+  TRY(vo_solve_launch(h->d_records, h->d_off, 2, h->d_x, h->prm.max_iterations, h->d_lm, P, st));
+  LOAM_HIP(hipEventRecord(h->ev[1], st));
+  return LOAM_OK;
+}
+
+// the read-back; every pending input becomes the pair's last solve
+int32_t vf_collect(loam_vo_frames* h, const VfStages& g) {
+  hipStream_t st = h->st;
+  const int P = h->P;
+  std::vector<double> x(6 * (size_t)P);
+  std::vector<loam_lm_stats> lm(P);
+  std::vector<VfCount> cnt(P);
+  LOAM_HIP(hipMemcpyAsync(x.data(), h->d_x, sizeof(double) * 6 * P, hipMemcpyDeviceToHost, st));
+  LOAM_HIP(hipMemcpyAsync(lm.data(), h->d_lm, sizeof(loam_lm_stats) * P, hipMemcpyDeviceToHost, st));
+  LOAM_HIP(hipMemcpyAsync(cnt.data(), h->d_cnt, sizeof(VfCount) * P, hipMemcpyDeviceToHost, st));
+  std::vector<GfState> gfs(g.detect ? P : 0);
+  if (g.detect) LOAM_HIP(hipMemcpyAsync(gfs.data(), h->gfb.state, sizeof(GfState) * P, hipMemcpyDeviceToHost, st));
+  LOAM_HIP(hipStreamSynchronize(st));
+  LOAM_HIP(hipEventElapsedTime(&h->ms, h->ev[0], h->ev[1]));
+  for (int p = 0; p < P; ++p) {
+    VfInput& in = h->rec[p].in;
+    const int mode = in.pair.mode;
+    if (mode == VF_NONE) continue;  // an idle pair keeps its earlier results
+    for (int i = 0; i < 6; ++i) h->x[6 * (size_t)p + i] = x[6 * (size_t)p + i];
+    h->lm[p] = lm[p];
+    h->cnt[p] = cnt[p];
+    const GfState gf = mode == VF_DETECT ? gfs[p] : GfState{};
+    const int n_tracks = mode == VF_DESC ? 0 : mode == VF_DETECT ? gf.n_corners : in.pair.n0;
+    h->rec[p].done = VfDone{mode, n_tracks, in.img, gf, false};
+    in = VfInput{};
+  }
   return LOAM_OK;
 }
 
@@ -478,20 +615,14 @@ int32_t loam_vo_frames_create(const loam_vo_frames_params* p, loam_depth* depth,
   TRY(alloc(h->d_x, P * 6));
   TRY(alloc(h->d_lm, P));
   TRY(alloc(h->d_cnt, P));
-  h->pairs.assign(P, VfPair{});
-  h->solved.assign(P, 0);
+  h->rec.assign(P, VfHost{});
   h->x0.assign(P * 6, 0.0);
   h->x.assign(P * 6, 0.0);
   h->lm.assign(P, loam_lm_stats{});
   h->cnt.assign(P, VfCount{});
   h->up.assign(P, VfPair{});
-  h->lk_in.assign(P, LkPair{});
-  h->lk_done.assign(P, LkPair{});
-  h->gf_in.assign(P, GfPair{});
-  h->gf_done.assign(P, GfPair{});
-  h->gf_state.assign(P, GfState{});
-  h->tracks_n.assign(P, -1);
-  h->tracks_mode.assign(P, VF_NONE);
+  h->lk_up.assign(P, LkPair{});
+  h->gf_up.assign(P, GfPair{});
   LOAM_HIP(hipStreamSynchronize(h->st));
   *out = h.release();
   return LOAM_OK;
@@ -525,8 +656,7 @@ int32_t loam_vo_frames_input_descriptors(loam_vo_frames* h, int32_t pair, const 
     LOAM_HIP(hipMemcpyAsync(h->d_kp1 + o, kp1_xy, sizeof(float2) * n1, hipMemcpyHostToDevice, h->st));
   }
   LOAM_HIP(hipStreamSynchronize(h->st));  // the caller's buffers are free after return
-  vf_replace(h, pair);
-  h->pairs[pair] = VfPair{VF_DESC, n0, n1, depth_stream_prev};
+  vf_replace(h, pair, VfInput{{VF_DESC, n0, n1, depth_stream_prev}, {}, 0});
   return LOAM_OK;
 }
 
@@ -546,19 +676,8 @@ int32_t loam_vo_frames_input_tracks(loam_vo_frames* h, int32_t pair, const float
     LOAM_HIP(hipMemcpyAsync(h->d_status + o, status, (size_t)n, hipMemcpyHostToDevice, h->st));
   }
   LOAM_HIP(hipStreamSynchronize(h->st));
-  vf_replace(h, pair);
-  h->pairs[pair] = VfPair{VF_TRACKS, n, n, depth_stream_prev};
+  vf_replace(h, pair, VfInput{{VF_TRACKS, n, n, depth_stream_prev}, {}, 0});
   return LOAM_OK;
-}
-
-void loam_lk_params_default(loam_lk_params* p) {
-  if (!p) return;
-  *p = loam_lk_params{};
-  p->win = 15;
-  p->max_level = 2;
-  p->max_count = 10;
-  p->epsilon = 0.03;
-  p->min_eig_threshold = 1e-4;
 }
 
 int32_t loam_vo_frames_enable_images(loam_vo_frames* h, const loam_lk_params* p) {
@@ -600,24 +719,13 @@ int32_t loam_vo_frames_input_images(loam_vo_frames* h, int32_t pair, const uint8
     set_error(std::string(who) + ": null input or bad image size");
     return LOAM_ERR_ARG;
   }
-  TRY(vf_put_images(h, pair, img_prev, img_curr, width, height, row_stride, who));
+  VfImage img;
+  TRY(vf_put_images(h, pair, img_prev, img_curr, width, height, row_stride, who, &img));
   if (n)
     LOAM_HIP(hipMemcpyAsync(h->d_kp0 + (size_t)pair * h->K, pts_xy, sizeof(float2) * n, hipMemcpyHostToDevice, h->st));
   LOAM_HIP(hipStreamSynchronize(h->st));
-  vf_replace(h, pair);
-  h->pairs[pair] = VfPair{VF_IMAGES, n, n, depth_stream_prev};
-  h->lk_in[pair] = LkPair{1, width, height, lk_levels(width, height, h->lk.win, h->lk.max_level), n};
+  vf_replace(h, pair, VfInput{{VF_IMAGES, n, n, depth_stream_prev}, img, 0});
   return LOAM_OK;
-}
-
-void loam_gftt_params_default(loam_gftt_params* p) {
-  if (!p) return;
-  *p = loam_gftt_params{};
-  p->max_corners = 1024;
-  p->quality_level = 0.03;
-  p->min_distance = 7.5;
-  p->block_size = 5;
-  p->max_candidates = 65536;
 }
 
 int32_t loam_vo_frames_enable_detection(loam_vo_frames* h, const loam_gftt_params* p) {
@@ -672,13 +780,10 @@ int32_t loam_vo_frames_input_image_pair(loam_vo_frames* h, int32_t pair, const u
     set_error(std::string(who) + ": detect_on is 0 (the previous image) or 1 (the current one)");
     return LOAM_ERR_ARG;
   }
-  TRY(vf_put_images(h, pair, img_prev, img_curr, width, height, row_stride, who));
+  VfImage img;
+  TRY(vf_put_images(h, pair, img_prev, img_curr, width, height, row_stride, who, &img));
   LOAM_HIP(hipStreamSynchronize(h->st));
-  vf_replace(h, pair);
-  h->pairs[pair] = VfPair{VF_DETECT, 0, 0, depth_stream_prev};  // the count is the device's
-  // n: the width of the tracker's grid; the detection writes the pair's own count over it
-  h->lk_in[pair] = LkPair{1, width, height, lk_levels(width, height, h->lk.win, h->lk.max_level), h->gf.max_corners};
-  h->gf_in[pair] = GfPair{1, width, height, detect_on};
+  vf_replace(h, pair, VfInput{{VF_DETECT, 0, 0, depth_stream_prev}, img, detect_on});
   return LOAM_OK;
 }
 
@@ -690,109 +795,22 @@ int32_t loam_vo_frames_set_initial(loam_vo_frames* h, int32_t pair, const double
 
 int32_t loam_vo_frames_solve(loam_vo_frames* h) {
   if (!h) return LOAM_ERR_ARG;
-  int active = 0, max_n0 = 0, max_n1 = 0;
-  bool match = false, images = false, detect = false;
-  for (const VfPair& p : h->pairs) {
-    if (p.mode == VF_NONE) continue;
-    ++active;
-    if (!depth_stream_processed(h->depth, p.stream)) {
-      set_error("loam_vo_frames_solve: depth stream " + std::to_string(p.stream) + " was never processed");
-      return LOAM_ERR_STATE;
-    }
-    images |= p.mode == VF_IMAGES || p.mode == VF_DETECT;
-    detect |= p.mode == VF_DETECT;
-    if (p.mode == VF_DESC && p.n0 > 0 && p.n1 >= 2) {
-      match = true;
-      max_n0 = std::max(max_n0, p.n0);
-      max_n1 = std::max(max_n1, p.n1);
-    }
-  }
-  if (!active) {
-    set_error("loam_vo_frames_solve: no pair has an input");
-    return LOAM_ERR_STATE;
-  }
+  VfStages g;
+  TRY(vf_plan(h, &g));
   DepthDev D;
   int dev;
   TRY(depth_device_view(h->depth, &D, &dev));
   LOAM_HIP(hipSetDevice(h->dev));
-  hipStream_t st = h->st;
-  const int P = h->P, K = h->K;
-  // slices of the train set: enough workgroups for two per CU, no slice thinner than a tile
-  const int qb = (max_n0 + VM_THREADS - 1) / VM_THREADS, tiles = (max_n1 + VM_TILE - 1) / VM_TILE;
-  int S = 1;
-  if (match) S = std::max(1, std::min({h->S_cap, tiles, (512 + qb * active - 1) / (qb * active)}));
-  h->up = h->pairs;
-  for (VfPair& p : h->up)
-    if (p.mode == VF_IMAGES || p.mode == VF_DETECT) p.mode = VF_TRACKS;  // once its points are tracked
-  LOAM_HIP(hipMemcpyAsync(h->d_pairs, h->up.data(), sizeof(VfPair) * P, hipMemcpyHostToDevice, st));
-  LOAM_HIP(hipMemcpyAsync(h->d_x, h->x0.data(), sizeof(double) * 6 * P, hipMemcpyHostToDevice, st));
-  if (images) LOAM_HIP(hipMemcpyAsync(h->d_lk, h->lk_in.data(), sizeof(LkPair) * P, hipMemcpyHostToDevice, st));
-  if (detect)
-    LOAM_HIP(hipMemcpyAsync(h->gfb.gf, h->gf_in.data(), sizeof(GfPair) * P, hipMemcpyHostToDevice, st));
-  LOAM_HIP(hipEventRecord(h->ev[0], st));
-  if (detect)  // after the tables' upload: it writes the corner counts into them
-    TRY(gftt_launch(h->gf, h->gfb, h->gf_in.data(), P, h->d_pyr, h->lk.image_bytes, h->d_kp0, K, h->d_pairs, h->d_lk,
-                    st));
-  if (images)
-    TRY(lk_launch(h->lk, h->d_lk, h->lk_in.data(), P, h->d_pyr, h->d_kp0, h->d_kp1, h->d_status, h->d_err, K, st));
-  if (match) {
-    const dim3 grid(qb, S, P);
-    if (h->WP == 8)
-      k_vo_match<8><<<grid, VM_THREADS, 0, st>>>(h->d_pairs, h->d_desc0, h->d_desc1, K, S, h->d_part);
-    else
-      k_vo_match<16><<<grid, VM_THREADS, 0, st>>>(h->d_pairs, h->d_desc0, h->d_desc1, K, S, h->d_part);
-  }
-  k_vo_merge<<<P, VA_THREADS, 0, st>>>(h->d_pairs, h->d_part, S, K, h->prm.match_ratio, h->d_status, h->d_matches,
-                                       h->d_cnt);
-  k_vo_assemble<<<P, VA_THREADS, 0, st>>>(h->d_pairs, h->d_matches, h->d_cnt, h->d_kp0, h->d_kp1, K, D, h->cam,
-                                          h->prm.remove_vo_outlier, h->prm.depth_radius, h->d_records, h->d_depth0,
-                                          h->d_off);
-  LOAM_HIP(hipGetLastError());
-  TRY(vo_solve_launch(h->d_records, h->d_off, 2, h->d_x, h->prm.max_iterations, h->d_lm, P, st));
-  LOAM_HIP(hipEventRecord(h->ev[1], st));
-  std::vector<double> x(6 * (size_t)P);
-  std::vector<loam_lm_stats> lm(P);
-  std::vector<VfCount> cnt(P);
-  LOAM_HIP(hipMemcpyAsync(x.data(), h->d_x, sizeof(double) * 6 * P, hipMemcpyDeviceToHost, st));
-  LOAM_HIP(hipMemcpyAsync(lm.data(), h->d_lm, sizeof(loam_lm_stats) * P, hipMemcpyDeviceToHost, st));
-  LOAM_HIP(hipMemcpyAsync(cnt.data(), h->d_cnt, sizeof(VfCount) * P, hipMemcpyDeviceToHost, st));
-  std::vector<GfState> gfs(detect ? P : 0);
-  if (detect) LOAM_HIP(hipMemcpyAsync(gfs.data(), h->gfb.state, sizeof(GfState) * P, hipMemcpyDeviceToHost, st));
-  LOAM_HIP(hipStreamSynchronize(st));
-  LOAM_HIP(hipEventElapsedTime(&h->ms, h->ev[0], h->ev[1]));
-  for (int p = 0; p < P; ++p) {
-    if (h->pairs[p].mode == VF_NONE) continue;  // an idle pair keeps its earlier results
-    for (int i = 0; i < 6; ++i) h->x[6 * (size_t)p + i] = x[6 * (size_t)p + i];
-    h->lm[p] = lm[p];
-    h->cnt[p] = cnt[p];
-    h->solved[p] = 1;
-    const int mode = h->pairs[p].mode;
-    h->tracks_n[p] = mode == VF_DESC ? -1 : mode == VF_DETECT ? gfs[p].n_corners : h->pairs[p].n0;
-    h->tracks_mode[p] = mode;
-    h->gf_state[p] = mode == VF_DETECT ? gfs[p] : GfState{};
-    if (mode == VF_IMAGES || mode == VF_DETECT) {
-      h->lk_done[p] = h->lk_in[p];
-      h->lk_done[p].n = h->tracks_n[p];
-      h->lk_in[p].active = 0;
-    }
-    if (mode == VF_DETECT) {
-      h->gf_done[p] = h->gf_in[p];
-      h->gf_in[p].active = 0;
-    }
-    h->pairs[p].mode = VF_NONE;
-  }
-  return LOAM_OK;
+  TRY(vf_enqueue(h, g, D));
+  return vf_collect(h, g);
 }
 
 int32_t loam_vo_frames_result(loam_vo_frames* h, int32_t pair, double* x6, loam_lm_stats* lm,
                               loam_vo_frame_stats* st) {
-  TRY(vf_check(h, pair, "loam_vo_frames_result"));
-  if (!h->solved[pair]) {
-    set_error("loam_vo_frames_result: the pair was never solved");
-    return LOAM_ERR_STATE;
-  }
-  const GfState& g = h->gf_state[pair];
-  if (g.n_cand > h->gf.max_cand && h->gf_on) {
+  const VfDone* d;
+  TRY(vf_last(h, pair, "loam_vo_frames_result", VF_DESC, "the pair was never solved", &d));
+  const GfState& g = d->gf;
+  if (d->mode == VF_DETECT && g.n_cand > h->gf.max_cand) {
     set_error("loam_vo_frames_result: the image has " + std::to_string(g.n_cand) +
               " corner candidates, more than max_candidates = " + std::to_string(h->gf.max_cand));
     return LOAM_ERR_CAPACITY;
@@ -817,11 +835,8 @@ int32_t loam_vo_frames_result(loam_vo_frames* h, int32_t pair, double* x6, loam_
 }
 
 int32_t loam_vo_frames_matches_copy(loam_vo_frames* h, int32_t pair, int32_t* out, int32_t cap) {
-  TRY(vf_check(h, pair, "loam_vo_frames_matches_copy"));
-  if (!h->solved[pair]) {
-    set_error("loam_vo_frames_matches_copy: the pair has no solved frame");
-    return LOAM_ERR_STATE;
-  }
+  const VfDone* d;
+  TRY(vf_last(h, pair, "loam_vo_frames_matches_copy", VF_DESC, "the pair has no solved frame", &d));
   const int n = h->cnt[pair].n_matches;
   if (n > cap || n == 0 || !out) return n;  // the count only
   LOAM_HIP(hipSetDevice(h->dev));
@@ -831,11 +846,8 @@ int32_t loam_vo_frames_matches_copy(loam_vo_frames* h, int32_t pair, int32_t* ou
 
 int32_t loam_vo_frames_records_copy(loam_vo_frames* h, int32_t pair, double* records, float* depth0,
                                     int32_t cap) {
-  TRY(vf_check(h, pair, "loam_vo_frames_records_copy"));
-  if (!h->solved[pair]) {
-    set_error("loam_vo_frames_records_copy: the pair has no solved frame");
-    return LOAM_ERR_STATE;
-  }
+  const VfDone* d;
+  TRY(vf_last(h, pair, "loam_vo_frames_records_copy", VF_DESC, "the pair has no solved frame", &d));
   const int n = h->cnt[pair].n_gated;
   if (n > cap || n == 0) return n;  // the count only
   LOAM_HIP(hipSetDevice(h->dev));
@@ -847,13 +859,11 @@ int32_t loam_vo_frames_records_copy(loam_vo_frames* h, int32_t pair, double* rec
 
 int32_t loam_vo_frames_tracks_copy(loam_vo_frames* h, int32_t pair, float* prev_xy, float* curr_xy,
                                    uint8_t* status, float* err, int32_t cap) {
-  TRY(vf_check(h, pair, "loam_vo_frames_tracks_copy"));
-  if (!h->solved[pair] || h->tracks_n[pair] < 0) {
-    set_error("loam_vo_frames_tracks_copy: the pair has no solved tracks (never solved, solved from descriptors, "
-              "or replaced by a later input)");
-    return LOAM_ERR_STATE;
-  }
-  const int n = h->tracks_n[pair];
+  const VfDone* d;
+  TRY(vf_last(h, pair, "loam_vo_frames_tracks_copy", VF_TRACKS,
+              "the pair has no solved tracks (never solved, solved from descriptors, or replaced by a later input)",
+              &d));
+  const int n = d->n_tracks;
   if (n > cap || n == 0) return n;  // the count only
   LOAM_HIP(hipSetDevice(h->dev));
   const size_t o = (size_t)pair * h->K;
@@ -861,7 +871,7 @@ int32_t loam_vo_frames_tracks_copy(loam_vo_frames* h, int32_t pair, float* prev_
   if (curr_xy) LOAM_HIP(hipMemcpy(curr_xy, h->d_kp1 + o, sizeof(float2) * n, hipMemcpyDeviceToHost));
   if (status) LOAM_HIP(hipMemcpy(status, h->d_status + o, (size_t)n, hipMemcpyDeviceToHost));
   if (err) {
-    if (h->tracks_mode[pair] == VF_IMAGES || h->tracks_mode[pair] == VF_DETECT)
+    if (d->mode == VF_IMAGES || d->mode == VF_DETECT)
       LOAM_HIP(hipMemcpy(err, h->d_err + o, sizeof(float) * n, hipMemcpyDeviceToHost));
     else
       std::fill(err, err + n, 0.f);
@@ -871,12 +881,10 @@ int32_t loam_vo_frames_tracks_copy(loam_vo_frames* h, int32_t pair, float* prev_
 
 int32_t loam_vo_frames_pyramid_copy(loam_vo_frames* h, int32_t pair, int32_t image, int32_t level, uint8_t* out,
                                     int32_t cap, int32_t* wh) {
-  TRY(vf_check(h, pair, "loam_vo_frames_pyramid_copy"));
-  if (!h->lk_on || !h->lk_done[pair].active) {
-    set_error("loam_vo_frames_pyramid_copy: the pair has no solved images (or a later input replaced them)");
-    return LOAM_ERR_STATE;
-  }
-  const LkPair& L = h->lk_done[pair];
+  const VfDone* d;
+  TRY(vf_last(h, pair, "loam_vo_frames_pyramid_copy", VF_IMAGES,
+              "the pair has no solved images (or a later input replaced them)", &d));
+  const VfImage& L = d->img;
   if (image < 0 || image > 1 || level < 0 || level >= L.levels) {
     set_error("loam_vo_frames_pyramid_copy: image is 0 or 1, level below the pair's level count");
     return LOAM_ERR_ARG;
@@ -899,12 +907,10 @@ int32_t loam_vo_frames_pyramid_copy(loam_vo_frames* h, int32_t pair, int32_t ima
 }
 
 int32_t loam_vo_frames_eig_copy(loam_vo_frames* h, int32_t pair, float* out, int32_t cap, int32_t* wh) {
-  TRY(vf_check(h, pair, "loam_vo_frames_eig_copy"));
-  if (!h->gf_on || !h->gf_done[pair].active) {
-    set_error("loam_vo_frames_eig_copy: the pair has no solved detection (or a later input replaced it)");
-    return LOAM_ERR_STATE;
-  }
-  const GfPair& G = h->gf_done[pair];
+  const VfDone* d;
+  TRY(vf_last(h, pair, "loam_vo_frames_eig_copy", VF_DETECT,
+              "the pair has no solved detection (or a later input replaced it)", &d));
+  const VfImage& G = d->img;
   if (wh) {
     wh[0] = G.w;
     wh[1] = G.h;

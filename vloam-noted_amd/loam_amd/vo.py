@@ -106,6 +106,18 @@ def gftt_params(**kw):
     return p
 
 
+def _image_pair(img_prev, img_curr):
+    """(a, b, w, h, row_stride): two (height, width) uint8 images of one size as arrays of one row
+    stride with dense rows (copied where they are not)"""
+    a, b = np.asarray(img_prev), np.asarray(img_curr)
+    if a.dtype != np.uint8 or b.dtype != np.uint8 or a.ndim != 2 or a.shape != b.shape:
+        raise ValueError("two 8-bit single-channel images of one size")
+    if a.size and (a.strides[1] != 1 or b.strides != a.strides):
+        a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    h, w = a.shape
+    return a, b, w, h, a.strides[0] if a.size else w
+
+
 class VOFrames:
     """The VO frame on the device (loam_vo_frames_*): ``n_pairs`` independent frame pairs, each
     from its descriptors (or LK tracks) to angles_0to1 / t_0to1 in one launch sequence per
@@ -162,16 +174,10 @@ class VOFrames:
     def input_images(self, pair, img_prev, img_curr, pts_xy, depth_stream_prev=0):
         """optical_flow_match from the images: two (height, width) uint8 images of one size (rows
         may be strided views) and the (n, 2) points of the previous image to track"""
-        a, b = np.asarray(img_prev), np.asarray(img_curr)
-        if a.dtype != np.uint8 or b.dtype != np.uint8 or a.ndim != 2 or a.shape != b.shape:
-            raise ValueError("two 8-bit single-channel images of one size")
-        if a.size and (a.strides[1] != 1 or b.strides != a.strides):
-            a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+        a, b, w, h, row_stride = _image_pair(img_prev, img_curr)
         pts = np.ascontiguousarray(pts_xy, dtype=np.float32).reshape(-1, 2)
-        h, w = a.shape
-        check(lib().loam_vo_frames_input_images(self.h, pair, a.ctypes.data, b.ctypes.data, w, h,
-                                                a.strides[0] if a.size else w, ptr(pts), len(pts),
-                                                depth_stream_prev))
+        check(lib().loam_vo_frames_input_images(self.h, pair, a.ctypes.data, b.ctypes.data, w, h, row_stride,
+                                                ptr(pts), len(pts), depth_stream_prev))
 
     def enable_detection(self, **kw):
         """allocate the corner detector's buffers of every pair (once, after enable_images); kw:
@@ -183,14 +189,9 @@ class VOFrames:
         """optical_flow_match from the two images alone: goodFeaturesToTrack on the previous image
         (detect_on 0) or the current one (1, the reference's order) runs on the device, and the
         corners are tracked from img_prev to img_curr"""
-        a, b = np.asarray(img_prev), np.asarray(img_curr)
-        if a.dtype != np.uint8 or b.dtype != np.uint8 or a.ndim != 2 or a.shape != b.shape:
-            raise ValueError("two 8-bit single-channel images of one size")
-        if a.size and (a.strides[1] != 1 or b.strides != a.strides):
-            a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-        h, w = a.shape
-        check(lib().loam_vo_frames_input_image_pair(self.h, pair, a.ctypes.data, b.ctypes.data, w, h,
-                                                    a.strides[0] if a.size else w, detect_on, depth_stream_prev))
+        a, b, w, h, row_stride = _image_pair(img_prev, img_curr)
+        check(lib().loam_vo_frames_input_image_pair(self.h, pair, a.ctypes.data, b.ctypes.data, w, h, row_stride,
+                                                    detect_on, depth_stream_prev))
 
     def eig(self, pair=0):
         """the (h, w) float32 minimum-eigenvalue plane of the pair's last detection"""
