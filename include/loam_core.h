@@ -537,8 +537,13 @@ int32_t loam_vo_solve(int32_t device, int32_t n_problems, const int32_t* offsets
  * the points to track (loam_vo_frames_input_images below: the cv::calcOpticalFlowPyrLK call of
  * ImageUtil::calculateOpticalFlow runs on the device in front of the rest), or the two images
  * alone (loam_vo_frames_input_image_pair: the cv::goodFeaturesToTrack call of
- * ImageUtil::detKeypoints runs on the device in front of the tracker).  ORB detection and
- * description stay with OpenCV.
+ * ImageUtil::detKeypoints runs on the device in front of the tracker).  optical_flow_match =
+ * false, the reference's default (vloam_main.launch:10): either the keypoints and their ORB
+ * descriptors, or the two images and the keypoints of both (loam_vo_frames_input_images_keypoints:
+ * the cv::ORB::create()->compute call of ImageUtil::descKeypoints runs on the device in front of the
+ * matcher), or the two images alone (loam_vo_frames_input_image_pair_match: detKeypoints on both
+ * images, descKeypoints, matchDescriptors and the solve, with no host step between them).  ORB's own
+ * FAST detector and its orientation are not here: the reference does not run them.
  * ------------------------------------------------------------------------------------ */
 typedef struct loam_vo_frames loam_vo_frames;
 typedef struct loam_vo_frames_params {
@@ -663,8 +668,63 @@ int32_t loam_vo_frames_input_image_pair(loam_vo_frames* h, int32_t pair, const u
                                         int32_t row_stride, int32_t detect_on, int32_t depth_stream_prev);
 /* for parity tests: the minimum-eigenvalue plane (cornerMinEigenVal) of the pair's last detection,
  * dense rows; wh (may be NULL) gets its width and height; copy when cap >= width * height; return
- * width * height */
+ * width * height.  After loam_vo_frames_input_image_pair_match, which detects on both images through
+ * one plane: the current image's */
 int32_t loam_vo_frames_eig_copy(loam_vo_frames* h, int32_t pair, float* out, int32_t cap, int32_t* wh);
+
+/* optical_flow_match = false from the images: cv::ORB::create()->compute (OpenCV 4.2 defaults:
+ * patchSize 31, edgeThreshold 31, WTA_K 2, 32 bytes) on given keypoints, as ImageUtil::descKeypoints
+ * calls it (image_util.cpp:280-339): one pyramid level at scale 1, no orientation (a keypoint keeps
+ * the angle it comes with; cv::KeyPoint's default, and detKeypoints', is -1 degree).
+ *  1. KeyPointsFilter::runByImageBorder(edge_threshold): a keypoint is kept iff edge_threshold <=
+ *     cvRound(x) < width - edge_threshold, the same for y, and none is if width or height <= 2 *
+ *     edge_threshold.  The order is kept; the kept list replaces the keypoints, and match indices
+ *     refer to it.  A keypoint with a coordinate that is not finite is dropped (OpenCV would read
+ *     out of bounds).
+ *  2. GaussianBlur 7 x 7, sigma 2, BORDER_REFLECT_101, as OpenCV's 8-bit fixed-point separable filter
+ *     computes it: weights cvRound(256 g) = 18 34 49 55 49 34 18, int32 sums, saturate_u8((sum +
+ *     32768) >> 16).
+ *  3. bit t % 8 of byte t / 8 is blur[c + P(2t)] < blur[c + P(2t + 1)] with c = (cvRound(x),
+ *     cvRound(y)) and P the learned pattern rotated by the keypoint's angle in float (two products
+ *     and one add or subtract, each rounded on its own) and rounded half to even. */
+typedef struct loam_orb_params {
+  int32_t edge_threshold;  /* 31; 22..32767 (the pattern reaches 19 pixels, the blur 3) */
+} loam_orb_params;
+void    loam_orb_params_default(loam_orb_params* p);
+/* allocates the blurred planes of every pair (once per handle, after loam_vo_frames_enable_images,
+ * whose max_width x max_height they are sized for).  LOAM_ERR_ARG: the handle's desc_bytes is not 32
+ * or edge_threshold outside its range; LOAM_ERR_STATE: before loam_vo_frames_enable_images, or
+ * already enabled; LOAM_ERR_CAPACITY: more than 2 GiB of planes */
+int32_t loam_vo_frames_enable_description(loam_vo_frames* h, const loam_orb_params* p);
+/* previous and current image as for loam_vo_frames_input_images, and the keypoints of both (2
+ * floats each; host memory, copied) with their angles in degrees (angle*_deg NULL: -1 for all).  The
+ * solve filters and describes them and goes on as if loam_vo_frames_input_descriptors had been
+ * given the kept keypoints and their descriptors: for a caller with a detector of their own.
+ * LOAM_ERR_STATE before loam_vo_frames_enable_description; LOAM_ERR_CAPACITY: an image over the
+ * maximum or n0 / n1 over max_keypoints */
+int32_t loam_vo_frames_input_images_keypoints(loam_vo_frames* h, int32_t pair, const uint8_t* img_prev,
+                                              const uint8_t* img_curr, int32_t width, int32_t height,
+                                              int32_t row_stride, const float* kp0_xy, const float* angle0_deg,
+                                              int32_t n0, const float* kp1_xy, const float* angle1_deg, int32_t n1,
+                                              int32_t depth_stream_prev);
+/* the two images alone, the reference's default path: the solve detects corners on both
+ * (loam_gftt_params: detKeypoints), describes them, matches and solves.  LOAM_ERR_STATE unless both
+ * loam_vo_frames_enable_detection and loam_vo_frames_enable_description were called.  An image with
+ * more than max_candidates candidates: as for loam_vo_frames_input_image_pair (the pair solves with
+ * no points, its loam_vo_frames_result returns LOAM_ERR_CAPACITY, other pairs are unaffected) */
+int32_t loam_vo_frames_input_image_pair_match(loam_vo_frames* h, int32_t pair, const uint8_t* img_prev,
+                                              const uint8_t* img_curr, int32_t width, int32_t height,
+                                              int32_t row_stride, int32_t depth_stream_prev);
+/* for parity tests and the node's match visualisation: the keypoints image 0 (previous) / 1
+ * (current) kept in the pair's last description, in order (2 floats each), and their 32-byte
+ * descriptors (each pointer may be NULL); copy when cap >= count; return count.  LOAM_ERR_STATE:
+ * never solved in these two modes, or a later input has replaced the data */
+int32_t loam_vo_frames_descriptors_copy(loam_vo_frames* h, int32_t pair, int32_t image, float* kp_xy,
+                                        uint8_t* desc, int32_t cap);
+/* for parity tests: the blurred plane of image 0 / 1 of the pair's last description, dense rows; wh
+ * (may be NULL) gets its width and height; copy when cap >= width * height; return width * height */
+int32_t loam_vo_frames_blur_copy(loam_vo_frames* h, int32_t pair, int32_t image, uint8_t* out, int32_t cap,
+                                 int32_t* wh);
 
 /* --------------------------------------------------------------------------------------
  * Device LM engine on an explicit factor list (lidarFactor.hpp + Ceres TR-LM).  Factor

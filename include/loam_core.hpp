@@ -252,6 +252,12 @@ inline loam_gftt_params default_gftt_params() {
   return p;
 }
 
+inline loam_orb_params default_orb_params() {
+  loam_orb_params p;
+  loam_orb_params_default(&p);
+  return p;
+}
+
 inline loam_vo_frames_params default_vo_frames_params() {
   loam_vo_frames_params p;
   loam_vo_frames_params_default(&p);
@@ -261,12 +267,18 @@ inline loam_vo_frames_params default_vo_frames_params() {
 // VisualOdometry::solveNlsAll with the matcher in front of it (visual_odometry.cpp:304-509,
 // image_util.cpp:347-438), n_pairs frame pairs per call: descriptors, LK tracks, or the two images
 // and the points to track (ImageUtil::calculateOpticalFlow's cv::calcOpticalFlowPyrLK on the device)
-// in, angles_0to1 / t_0to1 out.  `depth` is the loam_depth handle whose streams hold the previous
+// in, angles_0to1 / t_0to1 out; or, as the reference runs by default (optical_flow_match = false), the
+// two images alone: detKeypoints on both, descKeypoints (ORB) and matchDescriptors on the device.
+// `depth` is the loam_depth handle whose streams hold the previous
 // frames' buckets (point_cloud_utils[1 - i]); it must outlive this object.
 class VisualOdometryFrames {
  public:
   struct Match {  // cv::DMatch's fields
     int32_t queryIdx, trainIdx, distance;
+  };
+  struct Described {  // keypoints (x, y interleaved) the border filter kept, and their 32-byte descriptors
+    std::vector<float> kp_xy;
+    std::vector<uint8_t> desc;
   };
   struct Tracks {  // calcOpticalFlowPyrLK's prevPts, nextPts (x, y interleaved), status, err
     std::vector<float> prev_xy, curr_xy;
@@ -312,6 +324,28 @@ class VisualOdometryFrames {
     check(loam_vo_frames_input_image_pair(h_, pair, img_prev, img_curr, width, height, row_stride, detect_on,
                                           depth_stream_prev));
   }
+  // once, after enableImages: the blurred planes of every pair (cv::ORB::create()'s defaults)
+  void enableDescription(const loam_orb_params& p = default_orb_params()) {
+    check(loam_vo_frames_enable_description(h_, &p));
+  }
+  // optical_flow_match = false with a detector of one's own: the images and the keypoints of both
+  // (angles in degrees; nullptr: -1 for all, cv::KeyPoint's default); ImageUtil::descKeypoints' ORB
+  // compute runs on the device in front of the matcher
+  void inputImagesKeypoints(int32_t pair, const uint8_t* img_prev, const uint8_t* img_curr, int32_t width,
+                            int32_t height, int32_t row_stride, const float* kp0_xy, const float* angle0_deg,
+                            int32_t n0, const float* kp1_xy, const float* angle1_deg, int32_t n1,
+                            int32_t depth_stream_prev) {
+    check(loam_vo_frames_input_images_keypoints(h_, pair, img_prev, img_curr, width, height, row_stride, kp0_xy,
+                                                angle0_deg, n0, kp1_xy, angle1_deg, n1, depth_stream_prev));
+  }
+  // optical_flow_match = false from the two images alone (after enableDetection and
+  // enableDescription): VisualOdometry::processImage's detKeypoints, descKeypoints and
+  // matchDescriptors on both images, then the solve
+  void inputImagePairMatch(int32_t pair, const uint8_t* img_prev, const uint8_t* img_curr, int32_t width,
+                           int32_t height, int32_t row_stride, int32_t depth_stream_prev) {
+    check(loam_vo_frames_input_image_pair_match(h_, pair, img_prev, img_curr, width, height, row_stride,
+                                                depth_stream_prev));
+  }
   // angles_0to1 ++ t_0to1 the solves start from; nullptr: zeros (reset_VO_to_identity)
   void setInitial(int32_t pair, const double* x6 = nullptr) { check(loam_vo_frames_set_initial(h_, pair, x6)); }
   void solveNlsAll() { check(loam_vo_frames_solve(h_)); }
@@ -328,6 +362,16 @@ class VisualOdometryFrames {
     std::vector<Match> out(static_cast<size_t>(n));
     if (n) check(loam_vo_frames_matches_copy(h_, pair, &out[0].queryIdx, n));
     return out;
+  }
+  // the keypoints image 0 (previous) / 1 (current) kept in the pair's last description and their
+  // descriptors: what the matches' indices refer to (for cv::drawMatches)
+  Described descriptors(int32_t pair, int32_t image) const {
+    const int32_t n = check(loam_vo_frames_descriptors_copy(h_, pair, image, nullptr, nullptr, 0));
+    Described d;
+    d.kp_xy.resize(static_cast<size_t>(n) * 2);
+    d.desc.resize(static_cast<size_t>(n) * 32);
+    if (n) check(loam_vo_frames_descriptors_copy(h_, pair, image, d.kp_xy.data(), d.desc.data(), n));
+    return d;
   }
   // the tracks of the pair's last tracks / images solve (for the flow visualisation)
   Tracks tracks(int32_t pair) const {

@@ -22,7 +22,9 @@
 //                      is then resolved in order with ballots: the lowest pending lane is kept and
 //                      knocks out the later lanes within the distance.  A decision depends only on
 //                      earlier kept corners, so this is the sequential result.  Writes the corners
-//                      and, on the device, the count the tracker and the frame kernels read.
+//                      and, on the device, the count the tracker and the frame kernels read, where
+//                      the image's dst says (the previous image's keypoints for the tracker, or
+//                      either image's for the descriptors of orb.hip).
 //
 // The box sums are exact integers (OpenCV adds float products in an order its SIMD / IPP dispatch
 // decides); every float operation is a single one in calcMinEigenVal's order (-ffp-contract=off,
@@ -225,12 +227,13 @@ __global__ void __launch_bounds__(GF_SORT_THREADS) k_gftt_sort(const GfPair* gf,
 __global__ void __launch_bounds__(64) k_gftt_select(const GfPair* gf, GfState* state, const uint64_t* keys,
                                                     int cand_pad, int max_cand, int max_corners, double min_dist2,
                                                     int cell, int cell_cap, uint32_t* cells, int* cell_cnt,
-                                                    size_t cell_stride, float2* kp0, int K, VfPair* pairs,
-                                                    LkPair* lk) {
+                                                    size_t cell_stride, float2* kp0, float2* kp1, int K,
+                                                    VfPair* pairs, LkPair* lk) {
   const int p = blockIdx.x, lane = threadIdx.x;
   const GfPair G = gf[p];
   if (!G.active) return;
   const int w = G.w;
+  float2* kp = G.dst == GF_TO_KP1 ? kp1 : kp0;
   int n = state[p].n_cand;
   if (n > max_cand) n = 0;
   const uint64_t* Kp = keys + (size_t)p * cand_pad;
@@ -278,7 +281,7 @@ __global__ void __launch_bounds__(64) k_gftt_select(const GfPair* gf, GfState* s
     }
     const int rank = total + __popcll(kept & lanemask_lt());
     if (((kept >> lane) & 1) && rank < max_corners) {
-      kp0[(size_t)p * K + rank] = make_float2((float)x, (float)y);
+      kp[(size_t)p * K + rank] = make_float2((float)x, (float)y);
       if (cell) {
         const int c = cy * gw + cx;
         const int s = atomicAdd(&CC[c], 1);
@@ -299,9 +302,9 @@ __global__ void __launch_bounds__(64) k_gftt_select(const GfPair* gf, GfState* s
   if (lane == 0) {
     state[p].n_corners = total;
     state[p].err = __ballot(full) ? 1 : 0;
-    pairs[p].n0 = total;
-    pairs[p].n1 = total;
-    lk[p].n = total;
+    if (G.dst != GF_TO_KP1) pairs[p].n0 = total;
+    if (G.dst != GF_TO_KP0) pairs[p].n1 = total;
+    if (G.dst == GF_TO_TRACKS) lk[p].n = total;
   }
 }
 
@@ -352,7 +355,8 @@ int32_t gftt_plan(const loam_gftt_params* p, int max_keypoints, int max_w, int m
 }
 
 int32_t gftt_launch(const GfPlan& plan, const GfBuffers& B, const GfPair* pairs, int n_pairs, const uint8_t* d_pyr,
-                    size_t image_bytes, float2* d_kp0, int K, VfPair* d_pairs, LkPair* d_lk, hipStream_t st) {
+                    size_t image_bytes, float2* d_kp0, float2* d_kp1, int K, VfPair* d_pairs, LkPair* d_lk,
+                    hipStream_t st) {
   int w = 0, h = 0;
   for (int p = 0; p < n_pairs; ++p) {
     if (!pairs[p].active) continue;
@@ -368,7 +372,7 @@ int32_t gftt_launch(const GfPlan& plan, const GfBuffers& B, const GfPair* pairs,
   k_gftt_sort<<<n_pairs, GF_SORT_THREADS, 0, st>>>(B.gf, B.state, B.keys, plan.cand_pad, plan.max_cand);
   k_gftt_select<<<n_pairs, 64, 0, st>>>(B.gf, B.state, B.keys, plan.cand_pad, plan.max_cand, plan.max_corners,
                                         plan.min_dist2, plan.cell, plan.cell_cap, B.cells, B.cell_cnt,
-                                        plan.cell_stride, d_kp0, K, d_pairs, d_lk);
+                                        plan.cell_stride, d_kp0, d_kp1, K, d_pairs, d_lk);
   LOAM_HIP(hipGetLastError());
   return LOAM_OK;
 }

@@ -14,8 +14,13 @@ constexpr int GF_MAX_CANDIDATES = 1 << 22;
 struct GfPair {
   int active;  // 0: the pair is skipped
   int w, h;
-  int side;    // 0: the previous image of the pair's pyramid slot, 1: the current one
+  short side;  // 0: the previous image of the pair's pyramid slot, 1: the current one
+  short dst;   // GF_TO_*: where the corners and their count go
 };
+
+// corners -> d_kp0, count -> n0, n1 and the tracker's n (a detect pair: its corners are tracked);
+// corners -> d_kp0, count -> n0; corners -> d_kp1, count -> n1 (a match pair's two images)
+enum { GF_TO_TRACKS = 0, GF_TO_KP0 = 1, GF_TO_KP1 = 2 };
 
 // what the kernels leave per image
 struct GfState {
@@ -41,8 +46,8 @@ struct GfPlan {
 int32_t gftt_plan(const loam_gftt_params* p, int max_keypoints, int max_w, int max_h, GfPlan* out);
 
 struct GfBuffers {
-  GfPair* gf;          // [pair]
-  GfState* state;      // [pair]
+  GfPair* gf;          // [pair] of this launch
+  GfState* state;      // [pair] of this launch
   float* eig;          // [pair][eig_stride]
   uint64_t* keys;      // [pair][cand_pad]
   uint32_t* cells;     // [pair][cell_stride][cell_cap]
@@ -50,9 +55,11 @@ struct GfBuffers {
 };
 
 // corners of every active image: level 0 of the pair's pyramid slot (d_pyr, image_bytes per
-// pyramid) -> d_kp0 ([pair][K], selection order), the count into d_pairs[pair].n0 / n1 and
-// d_lk[pair].n.  Enqueues only, never waits.
+// pyramid) -> d_kp0 or d_kp1 ([pair][K], selection order), the count into d_pairs[pair].n0 / n1 and
+// d_lk[pair].n, as the image's dst says.  Launches on one stream may share B's scratch (eig, keys,
+// cells); each needs its own gf and state.  Enqueues only, never waits.
 int32_t gftt_launch(const GfPlan& plan, const GfBuffers& B, const GfPair* pairs, int n_pairs, const uint8_t* d_pyr,
-                    size_t image_bytes, float2* d_kp0, int K, VfPair* d_pairs, LkPair* d_lk, hipStream_t st);
+                    size_t image_bytes, float2* d_kp0, float2* d_kp1, int K, VfPair* d_pairs, LkPair* d_lk,
+                    hipStream_t st);
 
 }  // namespace loam

@@ -26,6 +26,12 @@
 // would have, and the kernels here see a tracks pair.  A pair given the images alone
 // (loam_vo_frames_input_image_pair) runs gftt.hip's corner detection in front of that: it leaves kp0
 // and, on the device, the point count in the pair tables the tracker and the kernels here read.
+// A pair given its two images and the keypoints of both (loam_vo_frames_input_images_keypoints), or
+// the images alone in the reference's default configuration (loam_vo_frames_input_image_pair_match:
+// gftt.hip on both images, one after the other through the same scratch), runs orb.hip's blur,
+// border filter and descriptors on the same stream: they leave kp0 / kp1 / desc0 / desc1 and the
+// kept counts as loam_vo_frames_input_descriptors would have, and the kernels here see a
+// descriptors pair.
 // No workgroup waits on another: the merge is a launch of its own.
 // Host: one VfHost per pair.  loam_vo_frames_solve plans (the stages to run and the kernels' tables,
 // from the pending inputs), enqueues (one launch sequence) and collects (the read-back; the pending
@@ -44,6 +50,7 @@
 #include "device_res.h"
 #include "gftt_dev.h"
 #include "lk_dev.h"
+#include "orb_dev.h"
 #include "vo_dev.h"
 #include "vo_frames_dev.h"
 
@@ -58,6 +65,7 @@ constexpr int VF_MAX_KEYPOINTS = 1 << 16;
 
 constexpr size_t VF_MAX_PYRAMID_BYTES = (size_t)2 << 30;
 constexpr size_t VF_MAX_DETECT_BYTES = (size_t)2 << 30;  // eigenvalue planes + candidate keys + cell grids
+constexpr size_t VF_MAX_BLUR_BYTES = (size_t)2 << 30;
 constexpr int VF_MAX_IMAGE_PAIRS = 32767;  // grid.z of the pyramid kernel = 2 * pairs
 
 struct VfCount {
@@ -296,13 +304,15 @@ struct VfInput {
   VfPair pair;
   VfImage img;
   int detect_on;
+  int rot[2];  // VF_DESCRIBE: the image's keypoints came with angles
 };
 struct VfDone {
   int mode;
-  int n_tracks;   // points in d_kp0 / d_kp1 / d_status (0 for VF_DESC)
+  int n_tracks;   // points in d_kp0 / d_kp1 / d_status (0 unless VF_TRACKS / VF_IMAGES / VF_DETECT)
+  int n_kept[2];  // keypoints the border filter kept (VF_DESCRIBE / VF_MATCH)
   VfImage img;
-  GfState gf;     // zero unless VF_DETECT
-  bool replaced;  // a later input has overwritten the keypoints, pyramids and eigenvalue plane
+  GfState gf[2];  // VF_DETECT: [0] the detection; VF_MATCH: the previous / current image's; else zero
+  bool replaced;  // a later input has overwritten the keypoints, pyramids, planes and descriptors
 };
 struct VfHost {
   VfInput in;
@@ -324,7 +334,8 @@ struct loam_vo_frames {
   std::vector<VfCount> cnt;
   std::vector<VfPair> up;       // a solve's tables, from rec[].in; they outlive the asynchronous uploads
   std::vector<LkPair> lk_up;
-  std::vector<GfPair> gf_up;
+  std::vector<GfPair> gf_up;    // [2][P]: the first and the second detection of a solve
+  std::vector<OrbPair> orb_up;
   DevPool pool;
   VfPair* d_pairs = nullptr;
   uint32_t *d_desc0 = nullptr, *d_desc1 = nullptr;  // [P][K][WP]
@@ -348,6 +359,12 @@ struct loam_vo_frames {
   bool gf_on = false;
   GfPlan gf{};
   GfBuffers gfb{};
+  GfPair* d_gf2 = nullptr;       // [P] the image table and the states of a solve's second detection (a match
+  GfState* d_state2 = nullptr;   // pair's current image): allocated once detection and description are enabled
+  // description (loam_vo_frames_enable_description)
+  bool orb_on = false;
+  OrbPlan orb{};
+  OrbBuffers orbb{};
   DevEvent ev[2];
   float ms = 0.f;
   ~loam_vo_frames() { (void)hipStreamSynchronize(st); }
@@ -413,13 +430,21 @@ void vf_replace(loam_vo_frames* h, int32_t pair, const VfInput& in) {
   h->rec[pair].in = in;
 }
 
-// the accessors' preamble: the pair's last solve, if it ran in min_mode or above (a mode leaves what
-// those below it leave; what those above VF_DESC add lies where a later input has written)
-int32_t vf_last(loam_vo_frames* h, int32_t pair, const char* who, int min_mode, const char* what,
+constexpr int vf_bit(int mode) { return 1 << mode; }
+constexpr int VF_ANY = ~vf_bit(VF_NONE);
+constexpr int VF_HAS_TRACKS = vf_bit(VF_TRACKS) | vf_bit(VF_IMAGES) | vf_bit(VF_DETECT);
+constexpr int VF_HAS_PYRAMIDS = vf_bit(VF_IMAGES) | vf_bit(VF_DETECT);
+constexpr int VF_HAS_EIG = vf_bit(VF_DETECT) | vf_bit(VF_MATCH);
+constexpr int VF_HAS_ORB = vf_bit(VF_DESCRIBE) | vf_bit(VF_MATCH);
+
+// the accessors' preamble: the pair's last solve, if it ran in one of `modes` (what every mode
+// leaves, the matches and the records, only a solve writes; the rest lies where a later input has
+// written)
+int32_t vf_last(loam_vo_frames* h, int32_t pair, const char* who, int modes, const char* what,
                 const VfDone** out) {
   TRY(vf_check(h, pair, who));
   *out = &h->rec[pair].done;
-  if ((*out)->mode < min_mode || (min_mode > VF_DESC && (*out)->replaced)) {
+  if (!(vf_bit((*out)->mode) & modes) || (modes != VF_ANY && (*out)->replaced)) {
     set_error(std::string(who) + ": " + what);
     return LOAM_ERR_STATE;
   }
@@ -439,6 +464,10 @@ int32_t vf_put_images(loam_vo_frames* h, int32_t pair, const uint8_t* img_prev, 
     return LOAM_ERR_CAPACITY;
   }
   LOAM_HIP(hipSetDevice(h->dev));
+  // from here on the pair's device data is being overwritten: what the last solve left there is gone,
+  // and so is a pending input, whether or not every copy below and in the caller succeeds
+  h->rec[pair].done.replaced = true;
+  h->rec[pair].in = VfInput{};
   uint8_t* lvl0 = h->d_pyr + (size_t)pair * 2 * h->lk.image_bytes;  // level 0: dense rows
   LOAM_HIP(hipMemcpy2DAsync(lvl0, width, img_prev, row_stride, width, height, hipMemcpyHostToDevice, h->st));
   LOAM_HIP(hipMemcpy2DAsync(lvl0 + h->lk.image_bytes, width, img_curr, row_stride, width, height,
@@ -447,9 +476,20 @@ int32_t vf_put_images(loam_vo_frames* h, int32_t pair, const uint8_t* img_prev, 
   return LOAM_OK;
 }
 
+// a match pair is detected on twice in a solve: the second image table and states, once the handle
+// both detects and describes (a handle that only detects allocates what it always did)
+int32_t vf_alloc_second_detection(loam_vo_frames* h) {
+  if (!h->gf_on || !h->orb_on || h->d_gf2) return LOAM_OK;
+  TRY(h->pool.alloc(&h->d_gf2, (size_t)h->P, h->st));
+  TRY(h->pool.alloc(&h->d_state2, (size_t)h->P, h->st));
+  LOAM_HIP(hipStreamSynchronize(h->st));
+  return LOAM_OK;
+}
+
 struct VfStages {  // what a solve runs
-  bool match, images, detect;
+  bool match, images, detect, detect2, orb;
   int qb, S;  // the matcher's query blocks and slices of the train set
+  int kb;     // no pair to describe has more keypoints per image
 };
 
 // the stages and the kernels' tables, from the pending inputs
@@ -460,11 +500,17 @@ int32_t vf_plan(loam_vo_frames* h, VfStages* out) {
     const VfInput& in = h->rec[p].in;
     const VfPair& q = in.pair;
     const bool images = q.mode == VF_IMAGES || q.mode == VF_DETECT, detect = q.mode == VF_DETECT;
+    const bool twice = q.mode == VF_MATCH, orb = twice || q.mode == VF_DESCRIBE;
     // an images / detect pair is a tracks pair once its points are tracked; a detect pair's n is the
-    // width of the tracker's grid until the detection writes the pair's own count over it
-    h->up[p] = VfPair{images ? VF_TRACKS : q.mode, q.n0, q.n1, q.stream};
+    // width of the tracker's grid until the detection writes the pair's own count over it.  A pair to
+    // describe is a descriptors pair once the border filter has written the kept counts over n0 / n1
+    // (a match pair's: over the two detections' counts)
+    h->up[p] = VfPair{images ? VF_TRACKS : orb ? VF_DESC : q.mode, q.n0, q.n1, q.stream};
     h->lk_up[p] = LkPair{images, in.img.w, in.img.h, in.img.levels, detect ? h->gf.max_corners : q.n0};
-    h->gf_up[p] = GfPair{detect, in.img.w, in.img.h, in.detect_on};
+    h->gf_up[p] = GfPair{detect || twice, in.img.w, in.img.h, (short)(twice ? 0 : in.detect_on),
+                         (short)(twice ? GF_TO_KP0 : GF_TO_TRACKS)};
+    h->gf_up[h->P + p] = GfPair{twice, in.img.w, in.img.h, 1, GF_TO_KP1};
+    h->orb_up[p] = OrbPair{orb, in.img.w, in.img.h, in.rot[0], in.rot[1]};
     if (q.mode == VF_NONE) continue;
     ++active;
     if (!depth_stream_processed(h->depth, q.stream)) {
@@ -472,11 +518,16 @@ int32_t vf_plan(loam_vo_frames* h, VfStages* out) {
       return LOAM_ERR_STATE;
     }
     g.images |= images;
-    g.detect |= detect;
-    if (q.mode == VF_DESC && q.n0 > 0 && q.n1 >= 2) {
+    g.detect |= detect || twice;
+    g.detect2 |= twice;
+    g.orb |= orb;
+    // the matcher's grid: a pair to describe has at most these keypoints (the counts are the device's)
+    const int b0 = twice ? h->gf.max_corners : q.n0, b1 = twice ? h->gf.max_corners : q.n1;
+    if (orb) g.kb = std::max({g.kb, b0, b1});
+    if ((q.mode == VF_DESC || orb) && b0 > 0 && b1 >= 2) {
       g.match = true;
-      max_n0 = std::max(max_n0, q.n0);
-      max_n1 = std::max(max_n1, q.n1);
+      max_n0 = std::max(max_n0, b0);
+      max_n1 = std::max(max_n1, b1);
     }
   }
   if (!active) {
@@ -487,7 +538,7 @@ int32_t vf_plan(loam_vo_frames* h, VfStages* out) {
   const int qb = (max_n0 + VM_THREADS - 1) / VM_THREADS, tiles = (max_n1 + VM_TILE - 1) / VM_TILE;
   int S = 1;
   if (g.match) S = std::max(1, std::min({h->S_cap, tiles, (512 + qb * active - 1) / (qb * active)}));
-  *out = VfStages{g.match, g.images, g.detect, qb, S};
+  *out = VfStages{g.match, g.images, g.detect, g.detect2, g.orb, qb, S, g.kb};
   return LOAM_OK;
 }
 
@@ -500,12 +551,25 @@ int32_t vf_enqueue(loam_vo_frames* h, const VfStages& g, const DepthDev& D) {
   if (g.images) LOAM_HIP(hipMemcpyAsync(h->d_lk, h->lk_up.data(), sizeof(LkPair) * P, hipMemcpyHostToDevice, st));
   if (g.detect)
     LOAM_HIP(hipMemcpyAsync(h->gfb.gf, h->gf_up.data(), sizeof(GfPair) * P, hipMemcpyHostToDevice, st));
+  if (g.detect2)
+    LOAM_HIP(hipMemcpyAsync(h->d_gf2, h->gf_up.data() + P, sizeof(GfPair) * P, hipMemcpyHostToDevice, st));
+  if (g.orb) LOAM_HIP(hipMemcpyAsync(h->orbb.orb, h->orb_up.data(), sizeof(OrbPair) * P, hipMemcpyHostToDevice, st));
   LOAM_HIP(hipEventRecord(h->ev[0], st));
   if (g.detect)  // after the tables' upload: it writes the corner counts into them
-    TRY(gftt_launch(h->gf, h->gfb, h->gf_up.data(), P, h->d_pyr, h->lk.image_bytes, h->d_kp0, K, h->d_pairs, h->d_lk,
-                    st));
+    TRY(gftt_launch(h->gf, h->gfb, h->gf_up.data(), P, h->d_pyr, h->lk.image_bytes, h->d_kp0, h->d_kp1, K, h->d_pairs,
+                    h->d_lk, st));
+  if (g.detect2) {  // the match pairs' current images, through the same scratch: the stream orders the two
+    GfBuffers second = h->gfb;
+    second.gf = h->d_gf2;
+    second.state = h->d_state2;
+    TRY(gftt_launch(h->gf, second, h->gf_up.data() + P, P, h->d_pyr, h->lk.image_bytes, h->d_kp0, h->d_kp1, K,
+                    h->d_pairs, h->d_lk, st));
+  }
   if (g.images)
     TRY(lk_launch(h->lk, h->d_lk, h->lk_up.data(), P, h->d_pyr, h->d_kp0, h->d_kp1, h->d_status, h->d_err, K, st));
+  if (g.orb)
+    TRY(orb_launch(h->orb, h->orbb, h->orb_up.data(), P, h->d_pyr, h->lk.image_bytes, h->d_kp0, h->d_kp1, h->d_desc0,
+                   h->d_desc1, K, g.kb, h->d_pairs, st));
   if (g.match) {
     const dim3 grid(g.qb, S, P);
     if (h->WP == 8)
@@ -534,8 +598,12 @@ int32_t vf_collect(loam_vo_frames* h, const VfStages& g) {
   LOAM_HIP(hipMemcpyAsync(x.data(), h->d_x, sizeof(double) * 6 * P, hipMemcpyDeviceToHost, st));
   LOAM_HIP(hipMemcpyAsync(lm.data(), h->d_lm, sizeof(loam_lm_stats) * P, hipMemcpyDeviceToHost, st));
   LOAM_HIP(hipMemcpyAsync(cnt.data(), h->d_cnt, sizeof(VfCount) * P, hipMemcpyDeviceToHost, st));
-  std::vector<GfState> gfs(g.detect ? P : 0);
+  std::vector<GfState> gfs(g.detect ? 2 * (size_t)P : 0);
   if (g.detect) LOAM_HIP(hipMemcpyAsync(gfs.data(), h->gfb.state, sizeof(GfState) * P, hipMemcpyDeviceToHost, st));
+  if (g.detect2)
+    LOAM_HIP(hipMemcpyAsync(gfs.data() + P, h->d_state2, sizeof(GfState) * P, hipMemcpyDeviceToHost, st));
+  std::vector<VfPair> kept(g.orb ? P : 0);  // the pair tables as the border filter left them
+  if (g.orb) LOAM_HIP(hipMemcpyAsync(kept.data(), h->d_pairs, sizeof(VfPair) * P, hipMemcpyDeviceToHost, st));
   LOAM_HIP(hipStreamSynchronize(st));
   LOAM_HIP(hipEventElapsedTime(&h->ms, h->ev[0], h->ev[1]));
   for (int p = 0; p < P; ++p) {
@@ -545,9 +613,18 @@ int32_t vf_collect(loam_vo_frames* h, const VfStages& g) {
     for (int i = 0; i < 6; ++i) h->x[6 * (size_t)p + i] = x[6 * (size_t)p + i];
     h->lm[p] = lm[p];
     h->cnt[p] = cnt[p];
-    const GfState gf = mode == VF_DETECT ? gfs[p] : GfState{};
-    const int n_tracks = mode == VF_DESC ? 0 : mode == VF_DETECT ? gf.n_corners : in.pair.n0;
-    h->rec[p].done = VfDone{mode, n_tracks, in.img, gf, false};
+    VfDone d{};
+    d.mode = mode;
+    d.img = in.img;
+    if (mode == VF_DETECT || mode == VF_MATCH) d.gf[0] = gfs[p];
+    if (mode == VF_MATCH) d.gf[1] = gfs[(size_t)P + p];
+    if (mode == VF_TRACKS || mode == VF_IMAGES) d.n_tracks = in.pair.n0;
+    if (mode == VF_DETECT) d.n_tracks = d.gf[0].n_corners;
+    if (mode == VF_DESCRIBE || mode == VF_MATCH) {
+      d.n_kept[0] = kept[p].n0;
+      d.n_kept[1] = kept[p].n1;
+    }
+    h->rec[p].done = d;
     in = VfInput{};
   }
   return LOAM_OK;
@@ -622,7 +699,8 @@ int32_t loam_vo_frames_create(const loam_vo_frames_params* p, loam_depth* depth,
   h->cnt.assign(P, VfCount{});
   h->up.assign(P, VfPair{});
   h->lk_up.assign(P, LkPair{});
-  h->gf_up.assign(P, GfPair{});
+  h->gf_up.assign(2 * P, GfPair{});
+  h->orb_up.assign(P, OrbPair{});
   LOAM_HIP(hipStreamSynchronize(h->st));
   *out = h.release();
   return LOAM_OK;
@@ -763,7 +841,7 @@ int32_t loam_vo_frames_enable_detection(loam_vo_frames* h, const loam_gftt_param
   h->gf = plan;
   h->gfb = B;
   h->gf_on = true;
-  return LOAM_OK;
+  return vf_alloc_second_detection(h);
 }
 
 int32_t loam_vo_frames_input_image_pair(loam_vo_frames* h, int32_t pair, const uint8_t* img_prev,
@@ -787,6 +865,154 @@ int32_t loam_vo_frames_input_image_pair(loam_vo_frames* h, int32_t pair, const u
   return LOAM_OK;
 }
 
+int32_t loam_vo_frames_enable_description(loam_vo_frames* h, const loam_orb_params* p) {
+  const char* who = "loam_vo_frames_enable_description";
+  if (!h || !p) {
+    set_error(std::string(who) + ": null handle or parameters");
+    return LOAM_ERR_ARG;
+  }
+  if (h->prm.desc_bytes != 4 * ORB_DESC_DWORDS || p->edge_threshold < ORB_MIN_EDGE || p->edge_threshold > ORB_MAX_EDGE) {
+    set_error(std::string(who) + ": desc_bytes is 32 for ORB, edge_threshold in 22..32767");
+    return LOAM_ERR_ARG;
+  }
+  if (!h->lk_on) {
+    set_error(std::string(who) + ": call loam_vo_frames_enable_images first");
+    return LOAM_ERR_STATE;
+  }
+  if (h->orb_on) {
+    set_error(std::string(who) + ": the handle already describes");
+    return LOAM_ERR_STATE;
+  }
+  OrbPlan plan{p->edge_threshold, (size_t)h->lk.max_w * h->lk.max_h};
+  if (plan.plane_stride > VF_MAX_BLUR_BYTES / 2 / (size_t)h->P) {
+    set_error(std::string(who) + ": more than 2 GiB of blurred planes");
+    return LOAM_ERR_CAPACITY;
+  }
+  LOAM_HIP(hipSetDevice(h->dev));
+  const size_t P = h->P, K = h->K;
+  OrbBuffers B{};
+  TRY(h->pool.alloc(&B.orb, P, h->st));
+  TRY(h->pool.alloc(&B.blur, P * 2 * plan.plane_stride, h->st));
+  TRY(h->pool.alloc(&B.rot0, P * K, h->st));
+  TRY(h->pool.alloc(&B.rot1, P * K, h->st));
+  TRY(h->pool.alloc(&B.uniform, (size_t)ORB_TESTS * 2, h->st));
+  int8_t xy[ORB_TESTS * 4];
+  orb_rotated_pattern(-1.f, xy);  // cv::KeyPoint's default angle
+  LOAM_HIP(hipMemcpyAsync(B.uniform, xy, sizeof(xy), hipMemcpyHostToDevice, h->st));
+  LOAM_HIP(hipStreamSynchronize(h->st));
+  h->orb = plan;
+  h->orbb = B;
+  h->orb_on = true;
+  return vf_alloc_second_detection(h);
+}
+
+int32_t loam_vo_frames_input_images_keypoints(loam_vo_frames* h, int32_t pair, const uint8_t* img_prev,
+                                              const uint8_t* img_curr, int32_t width, int32_t height,
+                                              int32_t row_stride, const float* kp0_xy, const float* angle0_deg,
+                                              int32_t n0, const float* kp1_xy, const float* angle1_deg, int32_t n1,
+                                              int32_t depth_stream_prev) {
+  const char* who = "loam_vo_frames_input_images_keypoints";
+  TRY(vf_check(h, pair, who));
+  if (!h->orb_on) {
+    set_error(std::string(who) + ": call loam_vo_frames_enable_description first");
+    return LOAM_ERR_STATE;
+  }
+  TRY(vf_check_input(h, pair, n0, n1, depth_stream_prev, who));
+  if ((n0 > 0 && !kp0_xy) || (n1 > 0 && !kp1_xy)) {
+    set_error(std::string(who) + ": null input or bad image size");
+    return LOAM_ERR_ARG;
+  }
+  const size_t o = (size_t)pair * h->K;
+  // (cos, sin) of the keypoints that come with an angle: the host's cosf / sinf, as OpenCV's
+  std::vector<float> cs[2];
+  const float* angles[2] = {n0 > 0 ? angle0_deg : nullptr, n1 > 0 ? angle1_deg : nullptr};
+  const float* kps[2] = {kp0_xy, kp1_xy};
+  float2* d_kp[2] = {h->d_kp0, h->d_kp1};
+  float2* d_rot[2] = {h->orbb.rot0, h->orbb.rot1};
+  const int n[2] = {n0, n1};
+  for (int s = 0; s < 2; ++s) {
+    if (!angles[s]) continue;
+    cs[s].resize(2 * (size_t)n[s]);
+    for (int i = 0; i < n[s]; ++i) orb_cos_sin(angles[s][i], &cs[s][2 * (size_t)i]);
+  }
+  VfImage img;
+  auto copies = [&]() -> int32_t {
+    TRY(vf_put_images(h, pair, img_prev, img_curr, width, height, row_stride, who, &img));
+    for (int s = 0; s < 2; ++s) {
+      if (n[s]) LOAM_HIP(hipMemcpyAsync(d_kp[s] + o, kps[s], sizeof(float2) * n[s], hipMemcpyHostToDevice, h->st));
+      if (angles[s])
+        LOAM_HIP(hipMemcpyAsync(d_rot[s] + o, cs[s].data(), sizeof(float2) * n[s], hipMemcpyHostToDevice, h->st));
+    }
+    return LOAM_OK;
+  };
+  const int32_t rc = copies();
+  const hipError_t drained = hipStreamSynchronize(h->st);  // also after a failure: cs and the caller's buffers are free
+  TRY(rc);
+  LOAM_HIP(drained);
+  img.levels = 1;  // no pyramid is built
+  vf_replace(h, pair, VfInput{{VF_DESCRIBE, n0, n1, depth_stream_prev}, img, 0, {angles[0] != nullptr, angles[1] != nullptr}});
+  return LOAM_OK;
+}
+
+int32_t loam_vo_frames_input_image_pair_match(loam_vo_frames* h, int32_t pair, const uint8_t* img_prev,
+                                              const uint8_t* img_curr, int32_t width, int32_t height,
+                                              int32_t row_stride, int32_t depth_stream_prev) {
+  const char* who = "loam_vo_frames_input_image_pair_match";
+  TRY(vf_check(h, pair, who));
+  if (!h->gf_on || !h->orb_on) {
+    set_error(std::string(who) + ": call loam_vo_frames_enable_detection and loam_vo_frames_enable_description first");
+    return LOAM_ERR_STATE;
+  }
+  TRY(vf_check_input(h, pair, 0, 0, depth_stream_prev, who));
+  VfImage img;
+  TRY(vf_put_images(h, pair, img_prev, img_curr, width, height, row_stride, who, &img));
+  img.levels = 1;  // no pyramid is built
+  LOAM_HIP(hipStreamSynchronize(h->st));
+  vf_replace(h, pair, VfInput{{VF_MATCH, 0, 0, depth_stream_prev}, img, 0, {0, 0}});
+  return LOAM_OK;
+}
+
+int32_t loam_vo_frames_descriptors_copy(loam_vo_frames* h, int32_t pair, int32_t image, float* kp_xy, uint8_t* desc,
+                                        int32_t cap) {
+  const VfDone* d;
+  TRY(vf_last(h, pair, "loam_vo_frames_descriptors_copy", VF_HAS_ORB,
+              "the pair has no solved description (or a later input replaced it)", &d));
+  if (image < 0 || image > 1) {
+    set_error("loam_vo_frames_descriptors_copy: image is 0 or 1");
+    return LOAM_ERR_ARG;
+  }
+  const int n = d->n_kept[image];
+  if (n > cap || n == 0) return n;  // the count only
+  LOAM_HIP(hipSetDevice(h->dev));
+  const size_t o = (size_t)pair * h->K;
+  if (kp_xy) LOAM_HIP(hipMemcpy(kp_xy, (image ? h->d_kp1 : h->d_kp0) + o, sizeof(float2) * n, hipMemcpyDeviceToHost));
+  if (desc)
+    LOAM_HIP(hipMemcpy(desc, (image ? h->d_desc1 : h->d_desc0) + o * h->WP, sizeof(uint32_t) * h->WP * n,
+                       hipMemcpyDeviceToHost));
+  return n;
+}
+
+int32_t loam_vo_frames_blur_copy(loam_vo_frames* h, int32_t pair, int32_t image, uint8_t* out, int32_t cap,
+                                 int32_t* wh) {
+  const VfDone* d;
+  TRY(vf_last(h, pair, "loam_vo_frames_blur_copy", VF_HAS_ORB,
+              "the pair has no solved description (or a later input replaced it)", &d));
+  if (image < 0 || image > 1) {
+    set_error("loam_vo_frames_blur_copy: image is 0 or 1");
+    return LOAM_ERR_ARG;
+  }
+  if (wh) {
+    wh[0] = d->img.w;
+    wh[1] = d->img.h;
+  }
+  const int n = d->img.w * d->img.h;
+  if (n > cap || !out) return n;  // the size only
+  LOAM_HIP(hipSetDevice(h->dev));
+  LOAM_HIP(hipMemcpy(out, h->orbb.blur + ((size_t)pair * 2 + image) * h->orb.plane_stride, (size_t)n,
+                     hipMemcpyDeviceToHost));
+  return n;
+}
+
 int32_t loam_vo_frames_set_initial(loam_vo_frames* h, int32_t pair, const double* x6) {
   TRY(vf_check(h, pair, "loam_vo_frames_set_initial"));
   for (int i = 0; i < 6; ++i) h->x0[(size_t)pair * 6 + i] = x6 ? x6[i] : 0.0;
@@ -808,16 +1034,17 @@ int32_t loam_vo_frames_solve(loam_vo_frames* h) {
 int32_t loam_vo_frames_result(loam_vo_frames* h, int32_t pair, double* x6, loam_lm_stats* lm,
                               loam_vo_frame_stats* st) {
   const VfDone* d;
-  TRY(vf_last(h, pair, "loam_vo_frames_result", VF_DESC, "the pair was never solved", &d));
-  const GfState& g = d->gf;
-  if (d->mode == VF_DETECT && g.n_cand > h->gf.max_cand) {
-    set_error("loam_vo_frames_result: the image has " + std::to_string(g.n_cand) +
-              " corner candidates, more than max_candidates = " + std::to_string(h->gf.max_cand));
-    return LOAM_ERR_CAPACITY;
-  }
-  if (g.err) {
-    set_error("loam_vo_frames_result: a cell of the corner grid was full");
-    return LOAM_ERR_CAPACITY;
+  TRY(vf_last(h, pair, "loam_vo_frames_result", VF_ANY, "the pair was never solved", &d));
+  for (const GfState& g : d->gf) {  // zero where the pair had no detection
+    if (g.n_cand > h->gf.max_cand) {
+      set_error("loam_vo_frames_result: the image has " + std::to_string(g.n_cand) +
+                " corner candidates, more than max_candidates = " + std::to_string(h->gf.max_cand));
+      return LOAM_ERR_CAPACITY;
+    }
+    if (g.err) {
+      set_error("loam_vo_frames_result: a cell of the corner grid was full");
+      return LOAM_ERR_CAPACITY;
+    }
   }
   if (x6)
     for (int i = 0; i < 6; ++i) x6[i] = h->x[(size_t)pair * 6 + i];
@@ -836,7 +1063,7 @@ int32_t loam_vo_frames_result(loam_vo_frames* h, int32_t pair, double* x6, loam_
 
 int32_t loam_vo_frames_matches_copy(loam_vo_frames* h, int32_t pair, int32_t* out, int32_t cap) {
   const VfDone* d;
-  TRY(vf_last(h, pair, "loam_vo_frames_matches_copy", VF_DESC, "the pair has no solved frame", &d));
+  TRY(vf_last(h, pair, "loam_vo_frames_matches_copy", VF_ANY, "the pair has no solved frame", &d));
   const int n = h->cnt[pair].n_matches;
   if (n > cap || n == 0 || !out) return n;  // the count only
   LOAM_HIP(hipSetDevice(h->dev));
@@ -847,7 +1074,7 @@ int32_t loam_vo_frames_matches_copy(loam_vo_frames* h, int32_t pair, int32_t* ou
 int32_t loam_vo_frames_records_copy(loam_vo_frames* h, int32_t pair, double* records, float* depth0,
                                     int32_t cap) {
   const VfDone* d;
-  TRY(vf_last(h, pair, "loam_vo_frames_records_copy", VF_DESC, "the pair has no solved frame", &d));
+  TRY(vf_last(h, pair, "loam_vo_frames_records_copy", VF_ANY, "the pair has no solved frame", &d));
   const int n = h->cnt[pair].n_gated;
   if (n > cap || n == 0) return n;  // the count only
   LOAM_HIP(hipSetDevice(h->dev));
@@ -860,7 +1087,7 @@ int32_t loam_vo_frames_records_copy(loam_vo_frames* h, int32_t pair, double* rec
 int32_t loam_vo_frames_tracks_copy(loam_vo_frames* h, int32_t pair, float* prev_xy, float* curr_xy,
                                    uint8_t* status, float* err, int32_t cap) {
   const VfDone* d;
-  TRY(vf_last(h, pair, "loam_vo_frames_tracks_copy", VF_TRACKS,
+  TRY(vf_last(h, pair, "loam_vo_frames_tracks_copy", VF_HAS_TRACKS,
               "the pair has no solved tracks (never solved, solved from descriptors, or replaced by a later input)",
               &d));
   const int n = d->n_tracks;
@@ -882,7 +1109,7 @@ int32_t loam_vo_frames_tracks_copy(loam_vo_frames* h, int32_t pair, float* prev_
 int32_t loam_vo_frames_pyramid_copy(loam_vo_frames* h, int32_t pair, int32_t image, int32_t level, uint8_t* out,
                                     int32_t cap, int32_t* wh) {
   const VfDone* d;
-  TRY(vf_last(h, pair, "loam_vo_frames_pyramid_copy", VF_IMAGES,
+  TRY(vf_last(h, pair, "loam_vo_frames_pyramid_copy", VF_HAS_PYRAMIDS,
               "the pair has no solved images (or a later input replaced them)", &d));
   const VfImage& L = d->img;
   if (image < 0 || image > 1 || level < 0 || level >= L.levels) {
@@ -908,7 +1135,7 @@ int32_t loam_vo_frames_pyramid_copy(loam_vo_frames* h, int32_t pair, int32_t ima
 
 int32_t loam_vo_frames_eig_copy(loam_vo_frames* h, int32_t pair, float* out, int32_t cap, int32_t* wh) {
   const VfDone* d;
-  TRY(vf_last(h, pair, "loam_vo_frames_eig_copy", VF_DETECT,
+  TRY(vf_last(h, pair, "loam_vo_frames_eig_copy", VF_HAS_EIG,
               "the pair has no solved detection (or a later input replaced it)", &d));
   const VfImage& G = d->img;
   if (wh) {

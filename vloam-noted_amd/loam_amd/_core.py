@@ -75,6 +75,10 @@ class GFTTParams(ctypes.Structure):
                 ("max_candidates", c_i32)]
 
 
+class ORBParams(ctypes.Structure):
+    _fields_ = [("edge_threshold", c_i32)]
+
+
 class VOFrameStats(ctypes.Structure):
     _fields_ = [("n_knn", c_i32), ("n_matches", c_i32), ("n_gated", c_i32), ("counter32", c_i32),
                 ("counter22", c_i32), ("ms", c_d)]
@@ -195,6 +199,13 @@ SIGNATURES = {
     "loam_vo_frames_enable_detection": (c_i32, [vp, ctypes.POINTER(GFTTParams)]),
     "loam_vo_frames_input_image_pair": (c_i32, [vp, c_i32, vp, vp, c_i32, c_i32, c_i32, c_i32, c_i32]),
     "loam_vo_frames_eig_copy": (c_i32, [vp, c_i32, vp, c_i32, vp]),
+    "loam_orb_params_default": (None, [ctypes.POINTER(ORBParams)]),
+    "loam_vo_frames_enable_description": (c_i32, [vp, ctypes.POINTER(ORBParams)]),
+    "loam_vo_frames_input_images_keypoints": (c_i32, [vp, c_i32, vp, vp, c_i32, c_i32, c_i32, vp, vp, c_i32, vp, vp,
+                                                      c_i32, c_i32]),
+    "loam_vo_frames_input_image_pair_match": (c_i32, [vp, c_i32, vp, vp, c_i32, c_i32, c_i32, c_i32]),
+    "loam_vo_frames_descriptors_copy": (c_i32, [vp, c_i32, c_i32, vp, vp, c_i32]),
+    "loam_vo_frames_blur_copy": (c_i32, [vp, c_i32, c_i32, vp, c_i32, vp]),
     "loam_lm_solve": (c_i32, [c_i32, vp, c_i32, vp, c_i32, ctypes.POINTER(LMStats)]),
     "loam_lm_normal_equations": (c_i32, [c_i32, vp, c_i32, vp, vp, vp, vp]),
     "loam_voxel_grid": (c_i32, [c_i32, vp, c_i32, c_f, vp, ctypes.POINTER(c_i32)]),

@@ -8,8 +8,9 @@ CostFunctor22 (epipolar).  ``solve`` runs any number of such problems on the dev
 workgroup per problem, every Ceres iteration on the GPU): HuberLoss(0.1), TR-LM, DENSE_QR,
 max_num_iterations = 100 (:70-74).
 
-``VOFrames`` is the whole frame on the device: descriptors, LK tracks, or the two images and the
-points to track (pyramidal Lucas-Kanade on the device) in, pose out, with the matcher, the gate,
+``VOFrames`` is the whole frame on the device: descriptors, LK tracks, the two images and the
+points to track (pyramidal Lucas-Kanade on the device), or the two images alone (Shi-Tomasi corners
+and, in the reference's default configuration, ORB descriptors on the device) in, pose out, with the matcher, the gate,
 the depth lookup and the records between them (``vo_factors`` stays the host
 definition the device records are checked against).  ``vo_to_velo_prior`` turns its solution into
 the prior of the coupled LiDAR odometry.
@@ -101,6 +102,15 @@ def gftt_params(**kw):
     minDistance 7.5, blockSize 5), 65536 candidates per image"""
     p = _core.GFTTParams()
     lib().loam_gftt_params_default(ctypes.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def orb_params(**kw):
+    """loam_orb_params: cv::ORB::create()'s edgeThreshold 31"""
+    p = _core.ORBParams()
+    lib().loam_orb_params_default(ctypes.byref(p))
     for k, v in kw.items():
         setattr(p, k, v)
     return p
@@ -199,6 +209,54 @@ class VOFrames:
         n = check(lib().loam_vo_frames_eig_copy(self.h, pair, None, 0, ptr(wh)))
         out = np.empty((int(wh[1]), int(wh[0])), np.float32)
         check(lib().loam_vo_frames_eig_copy(self.h, pair, ptr(out), n, None))
+        return out
+
+    def enable_description(self, **kw):
+        """allocate the blurred planes of every pair (once, after enable_images); kw: loam_orb_params
+        fields"""
+        self.orb = orb_params(**kw)
+        check(lib().loam_vo_frames_enable_description(self.h, ctypes.byref(self.orb)))
+
+    def input_images_keypoints(self, pair, img_prev, img_curr, kp0_xy, kp1_xy, angle0_deg=None, angle1_deg=None,
+                               depth_stream_prev=0):
+        """optical_flow_match = false from the images and keypoints of one's own: (n, 2) pixel
+        coordinates per image and, optionally, their angles in degrees (None: -1 for all, as
+        cv::KeyPoint's default); ORB's border filter and descriptors run on the device in front of the
+        matcher"""
+        a, b, w, h, row_stride = _image_pair(img_prev, img_curr)
+        k0 = np.ascontiguousarray(kp0_xy, dtype=np.float32).reshape(-1, 2)
+        k1 = np.ascontiguousarray(kp1_xy, dtype=np.float32).reshape(-1, 2)
+        a0 = None if angle0_deg is None else np.ascontiguousarray(angle0_deg, dtype=np.float32).reshape(-1)
+        a1 = None if angle1_deg is None else np.ascontiguousarray(angle1_deg, dtype=np.float32).reshape(-1)
+        if (a0 is not None and len(a0) != len(k0)) or (a1 is not None and len(a1) != len(k1)):
+            raise ValueError("one angle per keypoint")
+        # (an empty angle array is no array to the C side: -1 for all of no keypoints)
+        check(lib().loam_vo_frames_input_images_keypoints(
+            self.h, pair, a.ctypes.data, b.ctypes.data, w, h, row_stride, ptr(k0), ptr(a0), len(k0), ptr(k1), ptr(a1),
+            len(k1), depth_stream_prev))
+
+    def input_image_pair_match(self, pair, img_prev, img_curr, depth_stream_prev=0):
+        """the reference's default frame (optical_flow_match = false) from the two images alone:
+        goodFeaturesToTrack on both, ORB descriptors, the ratio-test matcher and the solve"""
+        a, b, w, h, row_stride = _image_pair(img_prev, img_curr)
+        check(lib().loam_vo_frames_input_image_pair_match(self.h, pair, a.ctypes.data, b.ctypes.data, w, h, row_stride,
+                                                          depth_stream_prev))
+
+    def descriptors(self, pair=0, image=0):
+        """(keypoints (n, 2) float32, descriptors (n, 32) uint8) image 0 (previous) / 1 (current) kept
+        in the pair's last description, in order: what the matches' indices refer to"""
+        n = check(lib().loam_vo_frames_descriptors_copy(self.h, pair, image, None, None, 0))
+        kp, desc = np.empty((n, 2), np.float32), np.empty((n, 32), np.uint8)
+        if n:
+            check(lib().loam_vo_frames_descriptors_copy(self.h, pair, image, ptr(kp), ptr(desc), n))
+        return kp, desc
+
+    def blur(self, pair=0, image=0):
+        """the (h, w) uint8 blurred plane the descriptors of the pair's last description sampled"""
+        wh = np.zeros(2, np.int32)
+        n = check(lib().loam_vo_frames_blur_copy(self.h, pair, image, None, 0, ptr(wh)))
+        out = np.empty((int(wh[1]), int(wh[0])), np.uint8)
+        check(lib().loam_vo_frames_blur_copy(self.h, pair, image, ptr(out), n, None))
         return out
 
     def set_initial(self, pair, x6=None):
